@@ -28,7 +28,15 @@ BASELINE.json config 3 ("Hyperband/ASHA sweep of ResNet-50 on synthetic ImageNet
   ``--target`` (set near the synthetic task's floor at this budget, so reaching it separates search strategies).
 
 ``value`` = trials completed in the timed region (all GPUs) / elapsed (max over ranks) × 3600.
+``ms_per_step`` = elapsed / ``--steps``: the wall time of one timed step (one complete sweep per GPU).
 Data: synthetic ImageNet-shape tensors generated on the device, random-init weights (no datasets available).
+
+A plain run sets up, warms up, times the sweeps and prints the result line; every figure of that line is read off
+the timed sweeps' own store rows.  ``--dump-outputs DIR`` also writes what the last timed step handed back -- each
+trial's metric and hyper-parameters -- as ``.npy`` arrays in a fixed order, for comparing two builds run with the same
+arguments (same sweep seeds, search space and data seed; a trial's loss still depends on where in the device data
+stream it trained and on the atomic weight-gradient reduction, so compare with a tolerance).  ``--full`` is where
+measurements beyond the headline belong (none today).
 """
 from __future__ import annotations
 
@@ -100,6 +108,16 @@ def _args(argv=None):
     ap.add_argument("--graph", type=int, default=int(os.environ.get("PLX_BENCH_GRAPH", "0")),
                     help="replay each training step as a captured (and verified) hipGraph; measured 8 %% slower than eager "
                          "launches for this step on ROCm 7.2 (10.5k vs 11.4k trials/h, same box)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy "
+                         "(float64): trial_loss.npy, the metric of every trial of that step's sweep(s), and "
+                         "trial_hparams.npy, one row per trial (columns in trial_hparams_columns.txt), both in the "
+                         "order (sweep, units, hyper-parameters).  The sweep seeds, the search space and the data seed "
+                         "depend only on the arguments, so two builds run with the same arguments compare row by row")
+    ap.add_argument("--full", action="store_true",
+                    help="also run whatever the benchmark measures beyond its headline figure (further baselines, "
+                         "precisions, configurations, reference comparisons).  Every figure of the result line comes out "
+                         "of the timed sweeps themselves, so today this adds nothing to a plain run")
     ap.add_argument("--cpu", action="store_true", help="CPU rehearsal (gloo, small ResNet, tiny images)")
     ap.add_argument("--control-only", action="store_true", help=argparse.SUPPRESS)  # internal: the scheduler process
     ap.add_argument("--verbose", action="store_true")
@@ -376,7 +394,23 @@ class ControlServer:
                                   "bo_beats_random": bool(rnd and bo and min(bo) < min(rnd)),
                                   "spread": round(max(allv) - min(allv), 4) if allv else None,
                                   "suggest": [it["data"].get("suggest") for it in its[1:]]})
+        dump = None
+        if self.args.dump_outputs:  # the last timed step: its sweep on every GPU (one BO group spans all of them)
+            last = gids[-(1 if self.args.config == "gpt2_bo" else self.world):]
+            lx = [x for x in xs if x["group_id"] in last]
+            cols = sorted({k for x in lx for k, v in (x.get("declarations") or {}).items()
+                           if isinstance(v, (int, float)) and not isinstance(v, bool)})
+            rows = []
+            for x in lx:
+                d = x.get("declarations") or {}
+                v = (x.get("last_metric") or {}).get("loss")
+                hp = [float(d.get(k, math.nan)) for k in cols]
+                rows.append((last.index(x["group_id"]), float(d.get("units", 0.0)), hp,
+                             float(v) if v is not None else math.nan))
+            rows.sort(key=lambda r: r[:3])
+            dump = {"columns": cols, "hparams": [r[2] for r in rows], "loss": [r[3] for r in rows]}
         return {"trials": trials, "succeeded": ok, "train_steps": steps, "ttt": ttt, "best": best, "per_sweep": per_sweep,
+                "dump": dump,
                 "bo_groups": bo_groups,
                 "per_units": per_units, "trial_devices": trial_devices,
                 "fsm_ok": fsm_ok, "resumed": resumed, "brackets": units, "groups": len(gids), "executors": execs,
@@ -468,6 +502,18 @@ def _pin_cpus(local_rank: int, world: int) -> list:
         except OSError:
             return []
     return cpus or []
+
+
+def _dump_outputs(path: str, dump: dict) -> None:
+    """``--dump-outputs``: the last timed step's trial metrics and hyper-parameters (a few hundred bytes per GPU)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    n, cols = len(dump["loss"]), dump["columns"]
+    np.save(os.path.join(path, "trial_loss.npy"), np.asarray(dump["loss"], dtype=np.float64))
+    np.save(os.path.join(path, "trial_hparams.npy"), np.asarray(dump["hparams"], dtype=np.float64).reshape(n, len(cols)))
+    with open(os.path.join(path, "trial_hparams_columns.txt"), "w") as f:
+        f.write("\n".join(cols) + "\n")
 
 
 def main() -> int:
@@ -627,6 +673,8 @@ def main() -> int:
         if msg is None or msg.get("ev") != "result":
             raise RuntimeError(f"control process failed: {msg}")
         res = msg["result"]
+        if args.dump_outputs:
+            _dump_outputs(args.dump_outputs, res["dump"])
         value = res["trials"] / elapsed_max * 3600.0
         n_exec = world // tg
         search = (f"hyperband max_iter={MAX_ITER} eta={ETA} resume=true, 3 brackets / 23 trials per sweep"

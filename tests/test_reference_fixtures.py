@@ -1,32 +1,25 @@
 """Golden parse tests against the reference's own Polyaxonfiles: every ``*_content`` spec of
 polyaxon/factories/fixtures.py:11-461 and every complete example in docs/templates/polyaxonfile_specification.
 
-The fixtures are read from the reference tree with ``ast`` (string literals only -- nothing of the reference is
-imported or executed); the tests skip when the reference tree is not mounted."""
-import ast
+The Polyaxonfiles themselves (YAML settings, nothing executable) are stored in tests/golden/
+reference_polyaxonfiles.json: ``fixtures`` maps every ``*_content`` name to its YAML, ``doc_examples`` lists the
+complete ``version:`` + ``kind:`` YAML blocks of the specification docs with the page each came from."""
+import json
 import os
-import re
-
-import pytest
 
 from polyaxon_amd.spec import specification_for
 from polyaxon_amd.spec.specification import GroupSpecification, Kinds
 
-REF = "/root/reference"
-FIXTURES = os.path.join(REF, "polyaxon", "factories", "fixtures.py")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_polyaxonfiles.json")
 
-pytestmark = pytest.mark.skipif(not os.path.exists(FIXTURES), reason="reference tree not mounted")
+
+def _golden():
+    with open(GOLDEN) as f:
+        return json.load(f)
 
 
 def _fixture_strings():
-    tree = ast.parse(open(FIXTURES).read())
-    out = {}
-    for node in tree.body:
-        if isinstance(node, ast.Assign) and isinstance(node.value, ast.Constant) and isinstance(node.value.value, str):
-            for t in node.targets:
-                if isinstance(t, ast.Name) and "_content" in t.id:
-                    out[t.id] = node.value.value
-    return out
+    return dict(_golden()["fixtures"])
 
 
 def test_every_reference_fixture_parses():
@@ -72,21 +65,12 @@ def test_fixture_semantics():
 
 
 def _doc_yaml_blocks():
-    import glob
-    import textwrap
-
-    for fn in sorted(glob.glob(os.path.join(REF, "docs", "templates", "**", "*.md"), recursive=True)):
-        txt = open(fn).read()
-        for block in re.findall(r"```yaml\n(.*?)```", txt, flags=re.S):
-            block = textwrap.dedent(block)
-            if re.search(r"^version:", block, flags=re.M) and re.search(r"^kind:", block, flags=re.M):
-                yield fn, block
+    for ex in _golden()["doc_examples"]:
+        yield ex["source"], ex["yaml"]
 
 
 def test_complete_doc_examples_parse():
     blocks = list(_doc_yaml_blocks())
-    if not blocks:
-        pytest.skip("no complete examples in the docs")
     assert len(blocks) >= 10
     for fn, block in blocks:
         spec = specification_for(block)

@@ -460,14 +460,20 @@ def test_resident_rejects_grid_random(tmp_path, cpu_pool_env):
         assert flow.store.list_groups() == []
 
 
-def test_bench_cpu_two_ranks_complete_sweeps():
-    """bench.py --gpus 2 spawns its own two ranks, times whole sweeps through polyflow and reports n_gpus: 2."""
+def test_bench_cpu_two_ranks_complete_sweeps(tmp_path):
+    """bench.py --gpus 2 spawns its own two ranks, times whole sweeps through polyflow and reports n_gpus: 2;
+    --dump-outputs writes the last timed step's trials (both GPUs' sweeps) as float64 arrays in a fixed order, and
+    --full is accepted."""
     import json
+
+    import numpy as np
 
     env = dict(os.environ, OMP_NUM_THREADS="2")
     env.pop("WORLD_SIZE", None)
+    dump = tmp_path / "out"
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--cpu", "--gpus", "2", "--steps", "1",
-                          "--warmup", "0"], capture_output=True, text=True, timeout=600, env=env, cwd="/tmp")
+                          "--warmup", "0", "--full", "--dump-outputs", str(dump)],
+                         capture_output=True, text=True, timeout=600, env=env, cwd="/tmp")
     assert out.returncode == 0, out.stderr[-3000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
     res = json.loads(line)
@@ -476,6 +482,15 @@ def test_bench_cpu_two_ranks_complete_sweeps():
     assert res["trials"] == 46 and res["trials_succeeded"] == 46
     assert res["store_fsm_history_ok"] is True
     assert res["value"] > 0 and res["ms_per_step"] > 0
+    assert res["ms_per_step"] == pytest.approx(max(r["elapsed_s"] for r in res["per_rank"]) * 1000.0, abs=1.0)
+    loss, hp = np.load(dump / "trial_loss.npy"), np.load(dump / "trial_hparams.npy")
+    cols = (dump / "trial_hparams_columns.txt").read_text().split()
+    assert cols == ["lr", "momentum", "units", "weight_decay"]
+    assert loss.dtype == np.float64 and hp.dtype == np.float64 and loss.shape == (46,) and hp.shape == (46, 4)
+    assert np.isfinite(hp).all() and np.nanmin(loss) == pytest.approx(res["best_loss"], abs=1e-4)
+    for half in (hp[:23], hp[23:]):  # per sweep: the 23 trials of its 3 brackets, ordered by their budget
+        assert half[:, cols.index("units")].tolist() == [1] * 9 + [3] * 8 + [9] * 5 + [27]
+    assert 0.02 <= hp[:, 0].min() and hp[:, 0].max() <= 1.0  # lr stays inside the search space
 
 
 def _bench(*extra, threads="1", timeout=900):
