@@ -1013,6 +1013,36 @@ PLX_API int plx_bn_backward_from_partials(const void* x, const uint8_t* mask, co
   return (int)hipGetLastError();
 }
 
+// Reduce + finalize only (dgamma, dbeta, coef), no dx pass: for a BatchNorm whose dx = coef[0] * dz + coef[1] * x +
+// coef[2] is produced by the data-gradient GEMM that consumes it (csrc/conv_gemm.hip plx_gemm_nt_bndx).  Arguments
+// as plx_bn_backward / plx_bn_backward_from_partials.
+PLX_API int plx_bn_backward_coef(const void* x, const uint8_t* mask, const void* dy, int64_t M, int C,
+                                 const float* gamma, const float* save_mean, const float* save_invstd, float* dgamma,
+                                 float* dbeta, float* coef, float* partials, int relu, int accumulate,
+                                 unsigned* counters, hipStream_t stream) {
+  Plan p;
+  if (!plan_for(M, C, &p) || M < 1 || (relu && mask == nullptr)) return 1;
+  float* pa = partials;
+  float* pb = partials + (int64_t)p.nblk * C;
+  hipLaunchKernelGGL(relu ? bn_bwd_reduce_kernel<true> : bn_bwd_reduce_kernel<false>, dim3(p.nblk, p.gy), dim3(kBlock), 0, stream, (const bf16x8*)x,
+                     mask, (const bf16x8*)dy, M, p.G, p.Gb, p.rows_per_block, save_mean, save_invstd,
+                     relu, pa, pb);
+  reduce_finalize_bwd(stream, partials, p.nblk, partials + 2 * (int64_t)p.nblk * C, counters,
+                      BwdFin{C, M, gamma, save_mean, save_invstd, dgamma, dbeta, coef, accumulate});
+  return (int)hipGetLastError();
+}
+
+PLX_API int plx_bn_backward_coef_from_partials(int64_t M, int C, const float* gamma, const float* save_mean,
+                                               const float* save_invstd, float* dgamma, float* dbeta, float* coef,
+                                               const float* partials, int nblk, float* l2, int accumulate,
+                                               unsigned* counters, hipStream_t stream) {
+  Plan p;
+  if (!plan_for(M, C, &p) || M < 1 || nblk < 1) return 1;
+  reduce_finalize_bwd(stream, partials, nblk, l2, counters,
+                      BwdFin{C, M, gamma, save_mean, save_invstd, dgamma, dbeta, coef, accumulate});
+  return (int)hipGetLastError();
+}
+
 // ---- ResNet stem BatchNorm + ReLU + 3x3/s2/p1 max-pool (see stem_apply_pool_kernel)
 // Forward: statistics (workspace `partials`: plx_bn_workspace(N*H*W, C) floats) -> mean / invstd / scale|bias ->
 // y [N][OH][OW][C] bf16 and idx [N*OH*OW*C] window positions.

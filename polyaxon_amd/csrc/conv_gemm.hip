@@ -3,6 +3,7 @@
 // On NHWC the three convolution passes are plain GEMMs over M = N*H*W pixel rows:
 //   forward      y[M][Cout]  = x[M][Cin]   . W[Cout][Cin]^T       -> plx_gemm_nt   (A = x,  B = W)
 //   data grad    dx[M][Cin]  = dy[M][Cout] . Wt[Cin][Cout]^T      -> plx_gemm_nt   (A = dy, B = W^T)
+//                the same with dy = the dx of the BatchNorm behind the conv, formed in the kernel -> plx_gemm_nt_bndx
 //   weight grad  dW[Cout][Cin] = sum_m dy[m][Cout]^T x[m][Cin]    -> plx_gemm_tn   (split over m, fp32 out)
 // plx_gemm_nt needs both operands K-contiguous (row-major [rows][K]); plx_gemm_tn reads both operands
 // row-major over the reduction index m and feeds the MFMA through ds_read_b64_tr_b16 transposed LDS reads.
@@ -23,6 +24,7 @@ namespace {
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((address_space(1))) const void gbl_void;
 
@@ -106,6 +108,18 @@ struct BnBwd {
     int skip_h, skip_w;
 };
 
+// BatchNorm-backward dx produced inside the data-gradient GEMM that consumes it (gemm_nt_kernel, BNDX).  The GEMM's A
+// operand is dy = A[k] * (g * mask) + B[k] * x + D[k] of a BatchNorm(+ReLU) with incoming gradient g (passed as the
+// GEMM's A pointer), input x and coefficient rows coef[3][K] (bn_bwd_finalize_kernel): the kernel forms it on the
+// global -> LDS path with the expression and the single bf16 rounding of bn_bwd_dx_kernel, writes it to dy once (the
+// weight gradient reads it) and feeds the rounded tile to the MFMAs.  g, x and dy are dense [M][K].
+struct BnDx {
+    const __bf16* x;
+    const uint8_t* mask;   // nullptr: no ReLU
+    const float* coef;
+    __bf16* dy;
+};
+
 __device__ __forceinline__ void row_coords(int m, int Hr, int Wr, int& n, int& r, int& c) {
     const int q = m / Wr;
     c = m - q * Wr;
@@ -184,14 +198,21 @@ __device__ __forceinline__ int nt_swz(int row) { return (row >> 1) & 7; }
 // profiles/r5_bn_fusion_bound.md).  Round 5 removed the 8-wave 3-stage ring variant (NBUF 3) and the 4-5 stage software pipeline (NBUF 4-5): both
 // measured slower in the training step than these lock-step kernels, profiles/r4_conv3x3_scratch_fix_ring_ab.jsonl,
 // r4_conv3x3_swp_ab.jsonl, r4_bench_swp4_conv.json.)
-template <int BM, int BN, int WGM, int WGN, int MODE, int MINB = 2, int NBUF = 2, bool BWD = false, int NTH = NTHREADS>
+// BNDX (dense data gradient, NBUF 2): the A operand is a BatchNorm backward's dx, produced here (BnDx).  B keeps the
+// LDS-DMA; each thread loads its 16-byte chunks of g and x, its mask bytes and its 8 channels' coefficients for stage
+// k+1 into registers before the MFMAs of stage k, transforms them afterwards and writes them into the other stage
+// buffer in the image the fragment reads expect; the tn == 0 block of a row panel also stores them to dy, after the
+// stage's barrier, so the stores have a whole stage to complete before the next vmcnt(0).
+template <int BM, int BN, int WGM, int WGN, int MODE, int MINB = 2, int NBUF = 2, bool BWD = false, int NTH = NTHREADS,
+          bool BNDX = false>
 __global__ void __launch_bounds__(NTH, MINB)
 gemm_nt_kernel(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf16* __restrict__ C,
                int M, int N, int K, int lda, int ldb, int ldc, const __bf16* __restrict__ zero,
                float* __restrict__ stats, ConvGeom geo, const __bf16* __restrict__ D, int ldd, BnBwd bnr,
-               const uint8_t* __restrict__ dmask) {
+               const uint8_t* __restrict__ dmask, BnDx bd) {
     constexpr bool CONV = MODE == 1, STEM = MODE == 2;
     static_assert(MODE >= 0 && MODE <= 2, "dense, gather or stem");
+    static_assert(!BNDX || (MODE == 0 && NBUF == 2 && BWD && NTH == 256), "BNDX: dense double-buffered data gradient");
     constexpr int NW = NTH / 64;                           // waves
     static_assert(WGM * WGN == NW, "one wave per wave tile");
     static_assert(NTH == 256 && NBUF >= 1 && NBUF <= 2, "4-wave kernels, one or two K stages");
@@ -314,19 +335,106 @@ gemm_nt_kernel(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf1
         st = tap_inner ? st_i : st_m;
         sc = tap_inner ? sc_i : sc_m;
     };
-    stage(0, 0, 0, 0);
-    advance();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
+    // BNDX staging state.  Chunk i of this thread is row (i * NW + wave) * 8 + lane / 8, physical 16-B chunk lane % 8
+    // of the stage image, i.e. logical chunk lc = lane % 8 ^ nt_swz(row) -- the same for every i (rows step by 32), so
+    // the thread keeps one 8-channel column and one set of coefficients per stage.  All of it moves through buffer
+    // resources: one 32-bit byte offset per chunk serves g, x and dy (the stage's k0 rides in the scalar offset), and
+    // rows past M get the out-of-range offset -- their loads return zeros, their stores are dropped.
+    constexpr int XI = BNDX ? AI : 1;
+    uint32_t e_off[XI];                                     // byte offset of the chunk at k0 = 0 (M * K * 2 < 2^31)
+    u32x4 gq[XI], xq[XI], oq[XI];
+    uint32_t mq[XI];
+    u32x4 cf[6];                                            // A | B | D of the thread's 8 channels
+    const int lc8 = (((lane & 7) ^ nt_swz(wave * 8 + (lane >> 3))) & 7) * 8;
+    const bool dy_owner = tn == 0;                          // one block per row panel stores dy
+    if constexpr (BNDX) {
+#pragma unroll
+        for (int i = 0; i < XI; ++i) {
+            const int gm = m0 + (i * NW + wave) * 8 + (lane >> 3);
+            e_off[i] = gm < M ? (uint32_t)((gm * K + lc8) * 2) : OOB;
+        }
+    }
+    auto load_a = [&](int k0) {
+        const __amdgpu_buffer_rsrc_t rx = buf_rsrc(bd.x), rc = buf_rsrc(bd.coef);
+#pragma unroll
+        for (int i = 0; i < XI; ++i) {
+            gq[i] = __builtin_amdgcn_raw_buffer_load_b128(ra, (int)e_off[i], k0 * 2, 0);
+            xq[i] = __builtin_amdgcn_raw_buffer_load_b128(rx, (int)e_off[i], k0 * 2, 0);
+        }
+        if (bd.mask != nullptr) {                           // 1 bit per element: byte (element offset / 8)
+            const __amdgpu_buffer_rsrc_t rm = buf_rsrc(bd.mask);
+#pragma unroll
+            for (int i = 0; i < XI; ++i)
+                mq[i] = __builtin_amdgcn_raw_buffer_load_b8(rm, (int)(e_off[i] == OOB ? OOB : e_off[i] >> 4), k0 >> 3, 0);
+        } else {
+#pragma unroll
+            for (int i = 0; i < XI; ++i) mq[i] = 0xffu;
+        }
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            cf[2 * r] = __builtin_amdgcn_raw_buffer_load_b128(rc, lc8 * 4, (r * K + k0) * 4, 0);
+            cf[2 * r + 1] = __builtin_amdgcn_raw_buffer_load_b128(rc, lc8 * 4 + 16, (r * K + k0) * 4, 0);
+        }
+    };
+    auto xform_a = [&](int buf) {                           // registers -> dy chunks (oq) -> stage image
+        char* base = smem + buf * STAGE;
+        const float* ca = (const float*)&cf[0];
+        const float* cb = (const float*)&cf[2];
+        const float* cd = (const float*)&cf[4];
+#pragma unroll
+        for (int i = 0; i < XI; ++i) {
+            const uint32_t* pg = (const uint32_t*)&gq[i];
+            const uint32_t* px = (const uint32_t*)&xq[i];
+            uint32_t* po = (uint32_t*)&oq[i];
+            const uint32_t mb = mq[i];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float g0 = (mb >> (2 * j)) & 1u ? __uint_as_float(pg[j] << 16) : 0.f;
+                const float g1 = (mb >> (2 * j + 1)) & 1u ? __uint_as_float(pg[j] & 0xffff0000u) : 0.f;
+                const float x0 = __uint_as_float(px[j] << 16), x1 = __uint_as_float(px[j] & 0xffff0000u);
+                const float o0 = fmaf(ca[2 * j], g0, fmaf(cb[2 * j], x0, cd[2 * j]));
+                const float o1 = fmaf(ca[2 * j + 1], g1, fmaf(cb[2 * j + 1], x1, cd[2 * j + 1]));
+                po[j] = pack_bf16x2(o0, o1);
+            }
+            if (e_off[i] == OOB) oq[i] = u32x4{0u, 0u, 0u, 0u};
+            *(u32x4*)(base + (i * NW + wave) * 1024 + lane * 16) = oq[i];
+        }
+    };
+    auto store_dy = [&](int k0) {
+        if (!dy_owner) return;
+        const __amdgpu_buffer_rsrc_t rd = buf_rsrc(bd.dy);
+#pragma unroll
+        for (int i = 0; i < XI; ++i) __builtin_amdgcn_raw_buffer_store_b128(oq[i], rd, (int)e_off[i], k0 * 2, 0);
+    };
+    if constexpr (BNDX) {
+        static_assert(!BNDX || NW == 4, "a thread's rows step by 32: one chunk column per thread");
+        load_a(0);
+        stage_b(0, 0, 0, 0);
+        xform_a(0);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        store_dy(0);
+    } else {
+        stage(0, 0, 0, 0);
+        advance();
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+    }
     for (int kt = 0; kt < nk; ++kt) {
         const int cur = NBUF == 2 ? kt & 1 : 0;
-        if (NBUF == 1 && kt > 0) {                          // restage the single buffer (the loop's tail barrier
+        if constexpr (BNDX) {
+            if (kt + 1 < nk) {
+                load_a((kt + 1) * BK);
+                stage_b(cur ^ 1, (kt + 1) * BK, 0, 0);
+            }
+        }
+        if (!BNDX && NBUF == 1 && kt > 0) {                 // restage the single buffer (the loop's tail barrier
             stage(0, kt * BK, st, sc);                      // retired its readers)
             advance();
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
         }
-        if (NBUF == 2 && kt + 1 < nk) {
+        if (!BNDX && NBUF == 2 && kt + 1 < nk) {
             stage(cur ^ 1, (kt + 1) * BK, st, sc);
             advance();
         }
@@ -353,8 +461,14 @@ gemm_nt_kernel(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf1
                 for (int rm = 0; rm < RM; ++rm)
                     acc[rn][rm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[rn], fb[rm], acc[rn][rm], 0, 0, 0);
         }
+        if constexpr (BNDX) {                               // the other buffer's readers retired at the last barrier
+            if (kt + 1 < nk) xform_a(cur ^ 1);
+        }
         if (NBUF == 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
+        if constexpr (BNDX) {
+            if (kt + 1 < nk) store_dy((kt + 1) * BK);
+        }
     }
     // Epilogue through LDS (the k-loop's last barrier freed it): D[n][m] has column m = fr and rows
     // n = 4*fq + r in each lane, i.e. 4 consecutive channels of one pixel.  Stage the bf16 tile as [m][n] rows
@@ -1106,7 +1220,25 @@ int launch_nt(const void* A, const void* B, void* C, int M, int N, int K, int ld
     auto k = bwd ? kb : kf;
     const int nwg = ((M + BM - 1) / BM) * (N / BN);
     hipLaunchKernelGGL(k, dim3(nwg), dim3(NTH), LDS, s, (const __bf16*)A, (const __bf16*)B, (__bf16*)C, M, N,
-                       K, lda, ldb, ldc, (const __bf16*)zero, stats, geo, (const __bf16*)D, ldd, bnr, dmask);
+                       K, lda, ldb, ldc, (const __bf16*)zero, stats, geo, (const __bf16*)D, ldd, bnr, dmask, BnDx{});
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+// The data-gradient GEMM that produces its A operand, a BatchNorm backward's dx (BnDx), double-buffered at 2 blocks
+// per CU.  g = the BatchNorm's incoming gradient (the kernel's A pointer), dense like bd.x and bd.dy (ld = K).
+template <int BM, int BN, int WGM, int WGN>
+int launch_nt_bndx(const void* g, const BnDx& bd, const void* B, void* C, int M, int N, int K, int ldb, int ldc,
+                   hipStream_t s, const void* D, int ldd, BnBwd bnr, const uint8_t* dmask) {
+    constexpr int TILE = BM * (BN * 2 + 16), RED = NTHREADS * 17 * 4;
+    constexpr int LDS = 2 * (BM + BN) * BK * 2;
+    static_assert(TILE <= LDS && RED <= LDS && LDS <= 80 * 1024, "epilogue staging fits; 2 blocks per CU");
+    auto k = gemm_nt_kernel<BM, BN, WGM, WGN, 0, 2, 2, true, NTHREADS, true>;
+    static int attr = set_lds(k, LDS);
+    if (attr) return attr;
+    const int nwg = ((M + BM - 1) / BM) * (N / BN);
+    hipLaunchKernelGGL(k, dim3(nwg), dim3(NTHREADS), LDS, s, (const __bf16*)g, (const __bf16*)B, (__bf16*)C, M, N, K, K,
+                       ldb, ldc, (const __bf16*)nullptr, (float*)nullptr, ConvGeom{}, (const __bf16*)D, ldd, bnr, dmask,
+                       bd);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
@@ -1376,6 +1508,28 @@ int plx_gemm_nt(const void* A, const void* B, void* C, int M, int N, int K, int 
     const bool one = nt_single(false, K, ((M + 255) / 256) * (N / 64));
     return one ? launch_nt<256, 64, 4, 1, false, 1>(A, B, C, M, N, K, lda, ldb, ldc, zero, stats, s, {}, D, ldd, b, dmask)
                : launch_nt<256, 64, 4, 1>(A, B, C, M, N, K, lda, ldb, ldc, zero, stats, s, {}, D, ldd, b, dmask);
+}
+
+// Data gradient of a 1x1 convolution whose incoming gradient is a BatchNorm backward's dx, produced in the kernel:
+//   dy[M][K] = bf16(coef[0][k] * (g * mask) + coef[1][k] * x + coef[2][k])      (bit-identical to bn_bwd_dx_kernel)
+//   C[M][N]  = dy . Wt[N][K]^T  (+ D, BatchNorm-backward partials: the epilogue arguments of plx_gemm_nt)
+// g, x, dy: dense bf16 [M][K]; mask (nullable): the BatchNorm's 1-bit ReLU mask; coef: fp32 [3][K] from the finalize.
+// With several N tiles per row panel (N > 128) every tile's block repeats the transform and only the first stores dy;
+// alone that ties (N = 256) or loses (N = 512) against the dx pass + plx_gemm_nt (profiles/bn_dx_fused.md), so the
+// Python side only sends N <= 128 here (ops/conv1x1.py dx_sink_for).
+int plx_gemm_nt_bndx(const void* g, const void* x, const uint8_t* mask, const float* coef, void* dy, const void* Wt,
+                     void* C, int M, int N, int K, int ldb, int ldc, const void* D, int ldd, const uint8_t* dmask,
+                     const BnBwd* bnr, void* stream) {
+    if (M <= 0 || N % 64 || K % BK || ldb % 8 || ldc % 8 || (D != nullptr && ldd % 8)) return -1;
+    if (g == nullptr || x == nullptr || coef == nullptr || dy == nullptr || dy == g || dy == x) return -1;
+    if ((long)M * K >= (1l << 30)) return -1;             // 32-bit byte offsets into g / x / dy
+    if (dmask != nullptr && (D == nullptr || ldd != N)) return -1;
+    if (bnr != nullptr && (ldc != N || bnr->part == nullptr)) return -1;
+    const BnBwd b = bnr != nullptr ? *bnr : BnBwd{};
+    const BnDx bd{(const __bf16*)x, mask, coef, (__bf16*)dy};
+    hipStream_t s = (hipStream_t)stream;
+    if (N % 128 == 0) return launch_nt_bndx<128, 128, 2, 2>(g, bd, Wt, C, M, N, K, ldb, ldc, s, D, ldd, b, dmask);
+    return launch_nt_bndx<256, 64, 4, 1>(g, bd, Wt, C, M, N, K, ldb, ldc, s, D, ldd, b, dmask);
 }
 
 // diagnostics: K slices (fp32 slabs) the weight-gradient plan of this problem uses (v2: wgrad_kernel's plan)

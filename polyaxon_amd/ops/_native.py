@@ -229,6 +229,8 @@ SIGNATURES: Dict[str, Dict[str, list]] = {
         "plx_bn_dx_blocks": [_L, _I],
         "plx_bn_backward_from_partials": [_P, _P, _P, _P, _P, _L, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _P,
                                           _P, _P],
+        "plx_bn_backward_coef": [_P, _P, _P, _L, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P],
+        "plx_bn_backward_coef_from_partials": [_L, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _P],
         "plx_stem_bn_pool_forward": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P, _P, _I, _P,
                                      _P],
         "plx_stem_bn_pool_bwd_workspace": [_I, _I, _I, _I],
@@ -259,6 +261,7 @@ SIGNATURES: Dict[str, Dict[str, list]] = {
     },
     "plx_conv": {
         "plx_gemm_nt": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P],
+        "plx_gemm_nt_bndx": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P],
         "plx_gemm_nt_rows_per_block": [_I],
         "plx_gemm_tn_workspace": [_I, _I, _I, _I],
         "plx_set_tn_v2": [_I, _I],

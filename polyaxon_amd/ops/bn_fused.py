@@ -48,8 +48,11 @@ def supported(x: torch.Tensor) -> bool:
 class _BNAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var, residual, momentum, eps, relu, ext=None, box=None,
-                link=None, rlink=None, defer=False):
+                link=None, rlink=None, defer=False, dxsink=None):
         lib = _native.lib("plx_bn")
+        # dxsink (ops.conv1x1.DxSink): x is a 1x1 convolution's output as is, and that convolution's data-gradient
+        # GEMM can produce this BatchNorm's dx (the backward decides)
+        ctx.dxsink = dxsink if x.is_contiguous(memory_format=torch.channels_last) else None
         x = _cl(x)
         n, c, h, w = x.shape
         m = n * h * w
@@ -140,6 +143,28 @@ class _BNAct(torch.autograd.Function):
             dg_ptr, db_ptr, acc = dgb.data_ptr(), dgb[c:].data_ptr(), 0
         coef = torch.empty(3 * c, **f32)
         part, nblk = ctx.link.take() if ctx.link is not None else (None, 0)
+        if ctx.dxsink is not None and dres is None:
+            # only dx to write: reduce / finalize here, and the data-gradient GEMM of the convolution that produced x
+            # forms dx = coef[0]·dz + coef[1]·x + coef[2] itself, into this (still unwritten) buffer
+            if part is not None:
+                l2 = torch.empty(_native.size("plx_bn", "plx_bn_l2_workspace", nblk, c), **f32)
+                rc = lib.plx_bn_backward_coef_from_partials(
+                    m, c, weight.data_ptr(), stats.data_ptr(), stats[c:].data_ptr(), dg_ptr, db_ptr, coef.data_ptr(),
+                    part.data_ptr(), nblk, l2.data_ptr(), acc, _counters(x.device), _stream())
+                _native.check(rc, "plx_bn_backward_coef_from_partials")
+            else:
+                partials = torch.empty(ctx.ws, **f32)
+                rc = lib.plx_bn_backward_coef(
+                    x.data_ptr(), mask.data_ptr() if mask is not None else None, dy.data_ptr(), m, c,
+                    weight.data_ptr(), stats.data_ptr(), stats[c:].data_ptr(), dg_ptr, db_ptr, coef.data_ptr(),
+                    partials.data_ptr(), int(ctx.relu), acc, _counters(x.device), _stream())
+                _native.check(rc, "plx_bn_backward_coef")
+            ctx.dxsink.put(dy, x, mask if ctx.relu else None, coef, dx)
+            if ctx.box is not None:  # masked_box (dres is None): dy and the mask ride into conv1's dgrad epilogue
+                ctx.box.put_masked(dy, mask)
+            dgamma = dgb[:c] if dgb is not None else None
+            dbeta = dgb[c:] if dgb is not None else None
+            return dx, dgamma, dbeta, None, None, None, None, None, None, None, None, None, None, None, None
         rb = None
         if ctx.rlink is not None and dres is not None:
             rl = ctx.rlink
@@ -173,7 +198,7 @@ class _BNAct(torch.autograd.Function):
             dres = None
         dgamma = dgb[:c] if dgb is not None else None
         dbeta = dgb[c:] if dgb is not None else None
-        return dx, dgamma, dbeta, None, None, dres, None, None, None, None, None, None, None, None
+        return dx, dgamma, dbeta, None, None, dres, None, None, None, None, None, None, None, None, None
 
 
 class _Materialize(torch.autograd.Function):
@@ -201,14 +226,16 @@ def materialize(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
 def bn_act(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, running_mean: Optional[torch.Tensor],
            running_var: Optional[torch.Tensor], training: bool, momentum: float, eps: float,
            residual: Optional[torch.Tensor], act: bool, ext_stats=None, residual_grad_box=None,
-           residual_link: bool = False, defer_apply: bool = False) -> torch.Tensor:
+           residual_link: bool = False, defer_apply: bool = False, dx_sink=None) -> torch.Tensor:
     """``ext_stats`` = (fp32 [2][nblk][C] channel sums / sums of squares of ``x``, nblk) from the op that
     produced ``x`` (the 1x1-conv GEMM epilogue); training mode then skips the stats pass.  ``residual_link``:
     ``residual`` is the output of a fused BatchNorm that nothing else consumes; its backward partials are then
     reduced by this op's dx pass.  ``defer_apply`` (training, no activation, no residual): skip the apply pass
     and return ``x`` itself marked ``_plx_deferred``; the fused BatchNorm that takes it as its residual applies
     the scale/bias while adding (a ResNet downsampling branch: ~0.3 ms of a bs-256 step), any other consumer
-    must call :func:`materialize` first."""
+    must call :func:`materialize` first.  ``dx_sink``: the :class:`~polyaxon_amd.ops.conv1x1.DxSink` the 1x1
+    convolution that produced ``x`` attached to it; the backward then leaves its dx pass to that convolution's
+    data-gradient GEMM whenever it has no d_residual tensor to write."""
     if residual is not None and residual.dtype != x.dtype:
         residual = residual.to(x.dtype)
     if training:
@@ -216,7 +243,7 @@ def bn_act(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, running_me
         rlink = getattr(residual, "_plx_bn_link", None) if (residual_link and residual is not None) else None
         defer = bool(defer_apply) and not act and residual is None
         y = _BNAct.apply(x, weight, bias, running_mean, running_var, residual, momentum, eps, act, ext_stats,
-                         residual_grad_box, link, rlink, defer)
+                         residual_grad_box, link, rlink, defer, dx_sink)
         y._plx_bn_link = link
         if defer:
             y._plx_deferred = True

@@ -15,6 +15,7 @@ gradient comes back in fp32, so autocast's bf16 weight copy and its backward cas
 from __future__ import annotations
 
 import ctypes
+import os
 from typing import Dict
 
 import torch
@@ -26,6 +27,17 @@ from polyaxon_amd.ops.flat import direct_grad
 
 _ZERO: Dict[int, torch.Tensor] = {}
 _CUS: Dict[int, int] = {}
+
+# A/B knob, read once at load: 1 = a BatchNorm backward hands its dx pass to the data-gradient GEMM of the 1x1
+# convolution that produced its input (DxSink, plx_gemm_nt_bndx); 0 = the dx pass and the GEMM as two kernels
+_BN_DX_FUSED = os.environ.get("PLX_BN_DX_FUSED", "1") != "0"
+
+
+def set_bn_dx_fused(on: bool) -> bool:
+    """Switch the fused BatchNorm-dx data gradient for the graphs built from now on; returns the previous setting."""
+    global _BN_DX_FUSED
+    prev, _BN_DX_FUSED = _BN_DX_FUSED, bool(on)
+    return prev
 
 
 def _zero_page(dev: torch.device) -> torch.Tensor:
@@ -77,6 +89,41 @@ def gemm_nt(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor = None, stats: t
                                              add_mask.data_ptr() if add_mask is not None else None,
                                              ctypes.addressof(bnr) if bnr is not None else None, _stream())
     _native.check(rc, "plx_gemm_nt")
+    return out
+
+
+def gemm_nt_bndx(g: torch.Tensor, x: torch.Tensor, mask: torch.Tensor, coef: torch.Tensor, dy: torch.Tensor,
+                 b: torch.Tensor, out: torch.Tensor = None, add: torch.Tensor = None,
+                 bnr: "_native.BnBwdArgs" = None, add_mask: torch.Tensor = None) -> torch.Tensor:
+    """The data gradient ``out[M][N] = dy · bᵀ`` of a 1x1 convolution whose incoming gradient ``dy[M][K]`` is a
+    BatchNorm backward's dx, produced by the GEMM itself: ``dy = coef[0]·(g·mask) + coef[1]·x + coef[2]`` per
+    channel, rounded to bf16 once (bit-identical to the standalone dx pass), written to ``dy`` and consumed as the
+    GEMM's A operand.  ``g``, ``x``, ``dy``: dense bf16 rows; ``mask``: the BatchNorm's 1-bit ReLU mask or None;
+    ``coef``: fp32 [3·K] from the BatchNorm backward's finalize; ``add`` / ``add_mask`` / ``bnr`` as
+    :func:`gemm_nt`."""
+    m, k = g.shape
+    n = b.shape[0]
+    if out is None:
+        out = torch.empty(m, n, dtype=torch.bfloat16, device=g.device)
+    for t in (g, x, dy):
+        assert t.shape == (m, k) and t.dtype == torch.bfloat16 and t.stride() == (k, 1) and t.data_ptr() % 16 == 0
+    assert b.stride(1) == 1 and out.stride(1) == 1 and b.shape[1] == k and b.dtype == torch.bfloat16
+    assert b.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0
+    assert coef.dtype == torch.float32 and coef.is_contiguous() and coef.numel() == 3 * k
+    if mask is not None:
+        assert mask.dtype == torch.uint8 and mask.numel() == m * k // 8
+    if add is not None:
+        assert add.shape == (m, n) and add.stride(1) == 1 and add.dtype == torch.bfloat16 and add.data_ptr() % 16 == 0
+    if add_mask is not None:
+        assert add is not None and add.stride(0) == n and add_mask.dtype == torch.uint8 and add_mask.numel() == m * n // 8
+    rc = _native.lib("plx_conv").plx_gemm_nt_bndx(g.data_ptr(), x.data_ptr(),
+                                                  mask.data_ptr() if mask is not None else None, coef.data_ptr(),
+                                                  dy.data_ptr(), b.data_ptr(), out.data_ptr(), m, n, k, b.stride(0),
+                                                  out.stride(0), add.data_ptr() if add is not None else None,
+                                                  add.stride(0) if add is not None else 0,
+                                                  add_mask.data_ptr() if add_mask is not None else None,
+                                                  ctypes.addressof(bnr) if bnr is not None else None, _stream())
+    _native.check(rc, "plx_gemm_nt_bndx")
     return out
 
 
@@ -169,6 +216,41 @@ def unpack_relu_mask(g: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
     return (g * keep).contiguous(memory_format=torch.channels_last)
 
 
+class DxSink:
+    """A 1x1 convolution's output → the fused BatchNorm that consumes it, for the backward: the BatchNorm hands its
+    dx pass to the convolution's data-gradient GEMM (:func:`gemm_nt_bndx`).
+
+    The convolution attaches one to its output (``y._plx_dx_sink``) when its data gradient is wide in K and narrow in
+    N (:func:`dx_sink_for`: the GEMM is bound by reading the gradient, which it can as well produce).  A BatchNorm backward
+    that only has dx to write (no d_residual tensor) runs its reduce / finalize, ``put``s what the dx pass would have
+    read and returns the *unwritten* dx buffer as its input gradient; the convolution's backward ``take``s the
+    payload, checks that the gradient it was handed is that very buffer, and its GEMM fills it on the way.  The
+    payload keeps the operands alive until then."""
+
+    __slots__ = ("payload",)
+
+    def __init__(self):
+        self.payload = None
+
+    def put(self, g: torch.Tensor, x: torch.Tensor, mask, coef: torch.Tensor, dx: torch.Tensor) -> None:
+        self.payload = (g, x, mask, coef, dx)
+
+    def take(self):
+        p, self.payload = self.payload, None
+        return p
+
+
+def dx_sink_for(x: torch.Tensor, weight: torch.Tensor):
+    """The shape-class rule of the fused BatchNorm-dx data gradient: the conv input needs a gradient, the GEMM's
+    K (= Cout) is at least twice its N (= Cin), and N fits one tile (N <= 128).  With two or four N tiles per row
+    panel every tile's block repeats the loads and the transform; measured alone that ties (N = 256) or loses
+    (N = 512) against the two kernels (profiles/bn_dx_fused.md), so those stay on them."""
+    if not _BN_DX_FUSED or not (torch.is_grad_enabled() and x.requires_grad):
+        return None
+    cout, cin = weight.shape[0], weight.shape[1]
+    return DxSink() if (cout >= 2 * cin and cin <= 128) else None
+
+
 class BnLink:
     """A fused BatchNorm(+ReLU)'s output → the convolution whose data gradient is that output's COMPLETE gradient.
 
@@ -239,9 +321,10 @@ def bn_link_of(x: torch.Tensor, want: bool):
 
 class _Conv1x1(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, stats, box, sink, link):
+    def forward(ctx, x, weight, stats, box, sink, link, dxsink=None):
         x = x.to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
         ctx.box = box
+        ctx.dxsink = dxsink
         ctx.sink = sink if (sink is not None and sink.armed) else None
         if ctx.sink is not None:
             ctx.sink.expect = True
@@ -263,6 +346,14 @@ class _Conv1x1(torch.autograd.Function):
     def backward(ctx, dy):
         x, wt = ctx.saved_tensors
         n, cin, h, w = x.shape
+        # the BatchNorm that consumed the output deferred its dx pass to this backward's data-gradient GEMM: the
+        # gradient handed over must be its still unwritten dx buffer (a hook or a second consumer of the output
+        # would have replaced it by a tensor computed from uninitialised memory)
+        fused = ctx.dxsink.take() if ctx.dxsink is not None else None
+        if fused is not None and (dy.data_ptr() != fused[4].data_ptr() or dy.shape != fused[4].shape
+                                  or dy.dtype != torch.bfloat16 or not ctx.needs_input_grad[0]):
+            raise RuntimeError("DxSink: the BatchNorm's deferred input gradient was replaced before the convolution's "
+                               "backward could fill it")
         dy = dy.to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
         dx = dw = None
         extra, extra_mask = ctx.box.take() if ctx.box is not None else (None, None)
@@ -282,8 +373,13 @@ class _Conv1x1(torch.autograd.Function):
                 bnr = ctx.link.request(-(-(n * h * w) // rows))
             elif ctx.link is not None and ctx.sink is not None and ctx.sink.s2k1 and extra is None:
                 bnr = ctx.link.request_split(-(-(n * h * w) // rows), -(-(n * ((h + 1) // 2) * ((w + 1) // 2)) // rows))
-            gemm_nt(_rows(dy), wt, _rows(dx), add=_rows(extra) if extra is not None else None, bnr=bnr,
-                    add_mask=extra_mask)
+            if fused is not None:  # fills dy (the BatchNorm's dx) and reads it as the A operand
+                g, bx, bmask, coef, _ = fused
+                gemm_nt_bndx(_rows(g), _rows(bx), bmask, coef, _rows(dy), wt, _rows(dx),
+                             add=_rows(extra) if extra is not None else None, bnr=bnr, add_mask=extra_mask)
+            else:
+                gemm_nt(_rows(dy), wt, _rows(dx), add=_rows(extra) if extra is not None else None, bnr=bnr,
+                        add_mask=extra_mask)
             if ctx.sink is not None:  # the downsample conv's dgrad adds this gradient in its epilogue
                 ctx.sink.put(dx)
                 dx = None
@@ -294,7 +390,7 @@ class _Conv1x1(torch.autograd.Function):
                 side_stream.run(lambda: gemm_tn(_rows(dy), _rows(x), out=slot, accumulate=True), (dy, x), x.device)
             else:
                 dw = gemm_tn(_rows(dy), _rows(x)).view(ctx.wshape).to(ctx.wdtype)
-        return dx, dw, None, None, None, None
+        return dx, dw, None, None, None, None, None
 
 
 def _bf16_context(x: torch.Tensor) -> bool:
@@ -325,9 +421,12 @@ def conv1x1(x: torch.Tensor, weight: torch.Tensor, with_stats: bool = False,
         stats = torch.empty(2 * nblk * cout, dtype=torch.float32, device=x.device)
     if grad_box is not None:
         grad_box.armed = True
-    y = _Conv1x1.apply(x, weight, stats, grad_box, grad_sink, bn_link_of(x, bn_link))
+    dxsink = dx_sink_for(x, weight)
+    y = _Conv1x1.apply(x, weight, stats, grad_box, grad_sink, bn_link_of(x, bn_link), dxsink)
     if stats is not None:
         y._plx_channel_stats = (stats, nblk)
+    if dxsink is not None:
+        y._plx_dx_sink = dxsink
     return y
 
 

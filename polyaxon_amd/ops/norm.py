@@ -61,7 +61,8 @@ class BatchNormAct(nn.Module):
                 ext = getattr(x, "_plx_channel_stats", None)  # set by ops.conv1x1 on its output
                 return bn_fused.bn_act(x, self.weight, self.bias, self.running_mean, self.running_var,
                                        self.training, self.momentum, self.eps, identity, self.act, ext,
-                                       residual_grad_box, residual_link, defer_apply)
+                                       residual_grad_box, residual_link, defer_apply,
+                                       getattr(x, "_plx_dx_sink", None))  # set by ops.conv1x1 on its output
         if identity is not None and identity.is_cuda:
             from polyaxon_amd.ops.bn_fused import materialize
             identity = materialize(identity)
