@@ -14,6 +14,14 @@
 //                     uniform / constant) so a new trial starts from fresh random weights in-place.
 //   plx_record_metric appends the step loss to a device ring and advances the device step counter.
 //   plx_commit_metric reduces the last `window` ring entries into a slot of the HPO metric tensor.
+//   plx_gradnorm_partials / plx_gradnorm_finalize
+//                     global-norm gradient clipping with a device-resident threshold (hp[5] = max_grad_norm): one
+//                     fp32 partial sum of squares per workgroup in a fixed order (no atomics; the combine happens at
+//                     the launch boundary), then a one-workgroup fp64 combine that publishes a 4-float state
+//                     {norm, scale, skipped steps, skip this step}.  plx_sgd_flat_clip / plx_adamw_flat_clip /
+//                     plx_adamw_mixed_clip read that state: they scale the gradient, or, on a non-finite norm, only
+//                     zero it.  Squares accumulate in fp32, so a gradient norm beyond about 1.8e19 (the square root
+//                     of FLT_MAX) overflows a partial and counts as non-finite: the step is skipped.
 //
 // All memory-bound kernels use 16-byte (float4) accesses and a grid capped at 2048 blocks with a
 // grid-stride loop (cdna_hip_programming.md Guideline 11/13).
@@ -40,20 +48,58 @@ inline int grid_for(int64_t n_vec, int cap = 2048) {
 int g_adamw_grid_cap = 2048;
 
 // ---------------------------------------------------------------- SGD
-// hp layout (fp32, device): [0] lr, [1] momentum, [2] weight_decay, [3] nesterov (0/1), [4] dampening
+// hp layout (fp32, device): [0] lr, [1] momentum, [2] weight_decay, [3] nesterov (0/1), [4] dampening,
+// [5] max_grad_norm (read by plx_gradnorm_finalize only; <= 0: no limit)
 // Elements [0, n_decay) receive weight decay (conv / linear weights), [n_decay, n) do not (BN, bias).
+//
+// CLIP (every optimizer kernel below): `state` is the clip state plx_gradnorm_finalize published for this step.
+// state[3] != 0 (non-finite norm): the kernel zeroes the gradients it owns and touches nothing else.  Otherwise the
+// gradient is multiplied by state[1] as a rounding step of its own (scale_grad: never contracted into what follows),
+// before weight decay and the moments -- a scale of exactly 1.0 therefore leaves the update bitwise what it is
+// without clipping.
+__device__ __forceinline__ float scale_grad(float g, float s) {
+#pragma clang fp contract(off)
+  return g * s;
+}
+
+// The clip state is a kernel argument of the CLIP = true instantiations only (an empty pack otherwise): the kernels
+// without clipping keep their argument lists -- an extra argument would move the hidden ones -- and so stay
+// instruction for instruction what they were before clipping existed.
+template <bool CLIP, typename... State>
+__device__ __forceinline__ const float* clip_state(State... state) {
+  static_assert(sizeof...(State) == (CLIP ? 1 : 0), "the clip state is passed exactly when CLIP");
+  if constexpr (CLIP)
+    return (state, ...);
+  else
+    return nullptr;
+}
+
+template <bool CLIP, typename... State>
 __global__ __launch_bounds__(kBlock) void sgd_flat_kernel(float4* __restrict__ p, float4* __restrict__ g,
                                                           float4* __restrict__ m, int64_t n_vec,
                                                           int64_t n_decay_vec, const float* __restrict__ hp,
-                                                          const int* __restrict__ first_step) {
+                                                          const int* __restrict__ first_step, State... state_arg) {
+  [[maybe_unused]] const float* const state = clip_state<CLIP>(state_arg...);
   const float lr = hp[0], mom = hp[1], wd = hp[2], damp = hp[4];
   const bool nesterov = hp[3] != 0.f;
   // First step after (re)initialisation: momentum buffer := grad (torch.optim.SGD semantics).
   const bool first = first_step != nullptr && *first_step == 0;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  [[maybe_unused]] float scale = 1.f;
+  if constexpr (CLIP) {
+    if (state[3] != 0.f) {
+      for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_vec; i += stride)
+        g[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+      return;
+    }
+    scale = state[1];
+  }
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_vec; i += stride) {
     float4 pv = p[i], gv = g[i], mv = m[i];
     const float w = i < n_decay_vec ? wd : 0.f;
+    if constexpr (CLIP)
+      gv = make_float4(scale_grad(gv.x, scale), scale_grad(gv.y, scale), scale_grad(gv.z, scale),
+                       scale_grad(gv.w, scale));
     float gg[4] = {gv.x + w * pv.x, gv.y + w * pv.y, gv.z + w * pv.z, gv.w + w * pv.w};
     float mm[4] = {mv.x, mv.y, mv.z, mv.w};
     float pp[4] = {pv.x, pv.y, pv.z, pv.w};
@@ -70,19 +116,34 @@ __global__ __launch_bounds__(kBlock) void sgd_flat_kernel(float4* __restrict__ p
 }
 
 // ---------------------------------------------------------------- AdamW
-// hp layout: [0] lr, [1] beta1, [2] beta2, [3] eps, [4] weight_decay. step = *step_ptr + 1.
+// hp layout: [0] lr, [1] beta1, [2] beta2, [3] eps, [4] weight_decay, [5] max_grad_norm (read by
+// plx_gradnorm_finalize only; <= 0: no limit). step = *step_ptr + 1.
+template <bool CLIP, typename... State>
 __global__ __launch_bounds__(kBlock) void adamw_flat_kernel(float4* __restrict__ p, float4* __restrict__ g,
                                                             float4* __restrict__ m, float4* __restrict__ v,
                                                             int64_t n_vec, int64_t n_decay_vec,
                                                             const float* __restrict__ hp,
-                                                            const int* __restrict__ step_ptr) {
+                                                            const int* __restrict__ step_ptr, State... state_arg) {
+  [[maybe_unused]] const float* const state = clip_state<CLIP>(state_arg...);
   const float lr = hp[0], b1 = hp[1], b2 = hp[2], eps = hp[3], wd = hp[4];
   const float t = (float)(*step_ptr + 1);
   const float bc1 = 1.f - __powf(b1, t), bc2 = 1.f - __powf(b2, t);
   const float step_size = lr / bc1, inv_sqrt_bc2 = rsqrtf(bc2);
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  [[maybe_unused]] float scale = 1.f;
+  if constexpr (CLIP) {
+    if (state[3] != 0.f) {
+      for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_vec; i += stride)
+        g[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+      return;
+    }
+    scale = state[1];
+  }
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_vec; i += stride) {
     float4 pv = p[i], gv = g[i], mv = m[i], vv = v[i];
+    if constexpr (CLIP)
+      gv = make_float4(scale_grad(gv.x, scale), scale_grad(gv.y, scale), scale_grad(gv.z, scale),
+                       scale_grad(gv.w, scale));
     const float decay = i < n_decay_vec ? (1.f - lr * wd) : 1.f;
     float pp[4] = {pv.x, pv.y, pv.z, pv.w}, gg[4] = {gv.x, gv.y, gv.z, gv.w};
     float mm[4] = {mv.x, mv.y, mv.z, mv.w}, vq[4] = {vv.x, vv.y, vv.z, vv.w};
@@ -124,17 +185,28 @@ __device__ __forceinline__ float adamw_elem(float p, float& m, float& v, float g
   return fmaf(p, decay, -((step_size * m) / denom));
 }
 
+template <bool CLIP, typename... State>
 __global__ __launch_bounds__(kBlock) void adamw_mixed_kernel(float4* __restrict__ p, u16x4* __restrict__ g,
                                                              float4* __restrict__ m, float4* __restrict__ v,
                                                              u16x4* __restrict__ plp, int64_t n_vec, int decay_on,
                                                              const float* __restrict__ hp,
-                                                             const int* __restrict__ step_ptr) {
+                                                             const int* __restrict__ step_ptr, State... state_arg) {
+  [[maybe_unused]] const float* const state = clip_state<CLIP>(state_arg...);
   const float lr = hp[0], b1 = hp[1], b2 = hp[2], eps = hp[3], wd = hp[4];
   const float t = (float)(*step_ptr + 1);
   const float bc1 = 1.f - __powf(b1, t), bc2 = 1.f - __powf(b2, t);
   const float step_size = lr / bc1, inv_sqrt_bc2 = rsqrtf(bc2);
   const float decay = decay_on ? (1.f - lr * wd) : 1.f;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  [[maybe_unused]] float scale = 1.f;
+  if constexpr (CLIP) {
+    if (state[3] != 0.f) {
+      for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_vec; i += stride)
+        g[i] = u16x4{0, 0, 0, 0};
+      return;
+    }
+    scale = state[1];
+  }
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_vec; i += stride) {
     const float4 pv = p[i], mv = m[i], vv = v[i];
     const u16x4 gv = g[i];
@@ -142,7 +214,9 @@ __global__ __launch_bounds__(kBlock) void adamw_mixed_kernel(float4* __restrict_
     u16x4 lo;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      pp[k] = adamw_elem(pp[k], mm[k], vq[k], bf16_to_f(gv[k]), b1, b2, eps, step_size, inv_sqrt_bc2, decay);
+      float gk = bf16_to_f(gv[k]);
+      if constexpr (CLIP) gk = scale_grad(gk, scale);
+      pp[k] = adamw_elem(pp[k], mm[k], vq[k], gk, b1, b2, eps, step_size, inv_sqrt_bc2, decay);
       lo[k] = f_to_bf16(pp[k]);
     }
     p[i] = make_float4(pp[0], pp[1], pp[2], pp[3]);
@@ -160,18 +234,32 @@ __global__ __launch_bounds__(kBlock) void adamw_mixed_kernel(float4* __restrict_
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 typedef unsigned short u16x8v __attribute__((ext_vector_type(8)));
 
-template <bool NT>
+template <bool NT, bool CLIP, typename... State>
 __global__ __launch_bounds__(kBlock) void adamw_mixed8_kernel(f32x4v* __restrict__ p, u16x8v* __restrict__ g,
                                                               f32x4v* __restrict__ m, f32x4v* __restrict__ v,
                                                               u16x8v* __restrict__ plp, int64_t n8, int decay_on,
                                                               const float* __restrict__ hp,
-                                                              const int* __restrict__ step_ptr) {
+                                                              const int* __restrict__ step_ptr, State... state_arg) {
+  [[maybe_unused]] const float* const state = clip_state<CLIP>(state_arg...);
   const float lr = hp[0], b1 = hp[1], b2 = hp[2], eps = hp[3], wd = hp[4];
   const float t = (float)(*step_ptr + 1);
   const float bc1 = 1.f - __powf(b1, t), bc2 = 1.f - __powf(b2, t);
   const float step_size = lr / bc1, inv_sqrt_bc2 = rsqrtf(bc2);
   const float decay = decay_on ? (1.f - lr * wd) : 1.f;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  [[maybe_unused]] float scale = 1.f;
+  if constexpr (CLIP) {
+    if (state[3] != 0.f) {
+      for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += stride) {
+        if constexpr (NT)
+          __builtin_nontemporal_store(u16x8v{0, 0, 0, 0, 0, 0, 0, 0}, g + i);
+        else
+          g[i] = u16x8v{0, 0, 0, 0, 0, 0, 0, 0};
+      }
+      return;
+    }
+    scale = state[1];
+  }
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += stride) {
     f32x4v pv[2], mv[2], vv[2];
 #pragma unroll
@@ -186,7 +274,9 @@ __global__ __launch_bounds__(kBlock) void adamw_mixed8_kernel(f32x4v* __restrict
     for (int k = 0; k < 8; ++k) {
       const int h = k >> 2, e = k & 3;
       float mk = mv[h][e], vk = vv[h][e];
-      const float pk = adamw_elem(pv[h][e], mk, vk, bf16_to_f(gv[k]), b1, b2, eps, step_size, inv_sqrt_bc2, decay);
+      float gk = bf16_to_f(gv[k]);
+      if constexpr (CLIP) gk = scale_grad(gk, scale);
+      const float pk = adamw_elem(pv[h][e], mk, vk, gk, b1, b2, eps, step_size, inv_sqrt_bc2, decay);
       mv[h][e] = mk;
       vv[h][e] = vk;
       pv[h][e] = pk;
@@ -223,6 +313,108 @@ __global__ __launch_bounds__(kBlock) void cast_lp_kernel(const float4* __restric
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_vec; i += stride) {
     const float4 pv = p[i];
     plp[i] = u16x4{f_to_bf16(pv.x), f_to_bf16(pv.y), f_to_bf16(pv.z), f_to_bf16(pv.w)};
+  }
+}
+
+// ---------------------------------------------------------------- global gradient norm (clipping)
+// One fp32 partial sum of squares per workgroup, combined by gradnorm_finalize_kernel at the launch boundary (no
+// atomics, no in-launch hand-off).  The grid is a function of n alone -- not of plx_set_adamw_grid_cap or any other
+// knob -- and every step of the reduction has a fixed order (one fused multiply-add per element into per-lane
+// accumulators, a pairwise combine of those, the wave shuffle tree, the waves through LDS), so the same gradients give
+// bitwise the same norm on every run and every rank.  Plain loads: the optimizer re-reads the gradients right after.
+constexpr int kNormGridCap = 2048;
+
+inline int gradnorm_blocks(int64_t n) { return grid_for(n >> 2, kNormGridCap); }
+
+__device__ __forceinline__ void block_sum_store(float acc, float* __restrict__ out) {
+  __shared__ float part[kBlock / 64];
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float t = part[0];
+    for (int k = 1; k < kBlock / 64; ++k) t += part[k];
+    *out = t;
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void gradnorm_f32_kernel(const float4* __restrict__ g, int64_t n_vec,
+                                                              float* __restrict__ partials) {
+  float a[4] = {0.f, 0.f, 0.f, 0.f};
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_vec; i += stride) {
+    const float4 gv = g[i];
+    a[0] = fmaf(gv.x, gv.x, a[0]);
+    a[1] = fmaf(gv.y, gv.y, a[1]);
+    a[2] = fmaf(gv.z, gv.z, a[2]);
+    a[3] = fmaf(gv.w, gv.w, a[3]);
+  }
+  block_sum_store((a[0] + a[1]) + (a[2] + a[3]), partials + blockIdx.x);
+}
+
+// bf16: 16-B loads of 8 elements over the 16-B aligned body [head, head + 8 n8); a range that starts or ends on an
+// 8-B boundary only (lp-mode bucket and segment offsets are 4-element aligned) has a 4-element head and / or tail,
+// which the grid's first thread takes.
+__global__ __launch_bounds__(kBlock) void gradnorm_bf16_kernel(const unsigned short* __restrict__ g, int head,
+                                                               int64_t n8, int tail, float* __restrict__ partials) {
+  float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (tid == 0) {
+    if (head) {
+      const u16x4 hv = *reinterpret_cast<const u16x4*>(g);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) a[k] = fmaf(bf16_to_f(hv[k]), bf16_to_f(hv[k]), a[k]);
+    }
+    if (tail) {
+      const u16x4 tv = *reinterpret_cast<const u16x4*>(g + head + 8 * n8);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) a[4 + k] = fmaf(bf16_to_f(tv[k]), bf16_to_f(tv[k]), a[4 + k]);
+    }
+  }
+  const u16x8v* __restrict__ body = reinterpret_cast<const u16x8v*>(g + head);
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = tid; i < n8; i += stride) {
+    const u16x8v gv = body[i];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) a[k] = fmaf(bf16_to_f(gv[k]), bf16_to_f(gv[k]), a[k]);
+  }
+  block_sum_store(((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7])), partials + blockIdx.x);
+}
+
+// One workgroup: the partials of every range of the step, summed in fp64 in a fixed order, and the clip state
+//   state[0] total norm of this step (before clipping)      state[1] scale the optimizer applies
+//   state[2] steps skipped since the last reset             state[3] 1.0 if this step is skipped, else 0.0
+// scale = min(1, max_norm / (norm + 1e-6)) (torch.nn.utils.clip_grad_norm_); max_norm = hp[5] <= 0: exactly 1.0,
+// the norm is still measured.  A non-finite norm skips the step: scale 0, state[2] += 1.
+__global__ __launch_bounds__(kBlock) void gradnorm_finalize_kernel(const float* __restrict__ partials, int n_partials,
+                                                                   const float* __restrict__ hp,
+                                                                   float* __restrict__ state) {
+  __shared__ double part[kBlock / 64];
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < n_partials; i += kBlock) acc += (double)partials[i];
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double ss = part[0];
+    for (int k = 1; k < kBlock / 64; ++k) ss += part[k];
+    const float norm = (float)sqrt(ss);
+    const float max_norm = hp[5];
+    const bool finite = (__float_as_uint(norm) & 0x7f800000u) != 0x7f800000u;
+    state[0] = norm;
+    if (!finite) {
+      state[1] = 0.f;
+      state[2] = state[2] + 1.f;
+      state[3] = 1.f;
+    } else {
+      float s = 1.f;
+      if (max_norm > 0.f) {
+        const float c = max_norm / (norm + 1e-6f);
+        s = c < 1.f ? c : 1.f;
+      }
+      state[1] = s;
+      state[3] = 0.f;
+    }
   }
 }
 
@@ -407,21 +599,115 @@ __global__ void commit_metric_kernel(const float* __restrict__ ring, const int* 
 
 }  // namespace
 
-PLX_API int plx_sgd_flat(float* p, float* g, float* m, int64_t n, int64_t n_decay, const float* hp,
-                         const int* first_step, hipStream_t stream) {
+// The optimizer launches, shared by the plain entry points (state == nullptr: the kernels without clipping) and the
+// *_clip ones.
+namespace {
+
+int launch_sgd_flat(float* p, float* g, float* m, int64_t n, int64_t n_decay, const float* hp, const int* first_step,
+                    const float* state, hipStream_t stream) {
   if ((n & 3) || (n_decay & 3)) return 1;  // caller pads flat buffers to a multiple of 4 floats
   const int64_t nv = n >> 2;
-  hipLaunchKernelGGL(sgd_flat_kernel, dim3(grid_for(nv)), dim3(kBlock), 0, stream, (float4*)p, (float4*)g,
-                     (float4*)m, nv, n_decay >> 2, hp, first_step);
+  if (state != nullptr)
+    hipLaunchKernelGGL((sgd_flat_kernel<true, const float*>), dim3(grid_for(nv)), dim3(kBlock), 0, stream, (float4*)p, (float4*)g,
+                       (float4*)m, nv, n_decay >> 2, hp, first_step, state);
+  else
+    hipLaunchKernelGGL(sgd_flat_kernel<false>, dim3(grid_for(nv)), dim3(kBlock), 0, stream, (float4*)p, (float4*)g,
+                       (float4*)m, nv, n_decay >> 2, hp, first_step);
   return (int)hipGetLastError();
+}
+
+int launch_adamw_flat(float* p, float* g, float* m, float* v, int64_t n, int64_t n_decay, const float* hp,
+                      const int* step, const float* state, hipStream_t stream) {
+  if ((n & 3) || (n_decay & 3)) return 1;
+  const int64_t nv = n >> 2;
+  const dim3 grid(grid_for(nv, g_adamw_grid_cap));
+  if (state != nullptr)
+    hipLaunchKernelGGL((adamw_flat_kernel<true, const float*>), grid, dim3(kBlock), 0, stream, (float4*)p, (float4*)g, (float4*)m,
+                       (float4*)v, nv, n_decay >> 2, hp, step, state);
+  else
+    hipLaunchKernelGGL(adamw_flat_kernel<false>, grid, dim3(kBlock), 0, stream, (float4*)p, (float4*)g, (float4*)m,
+                       (float4*)v, nv, n_decay >> 2, hp, step);
+  return (int)hipGetLastError();
+}
+
+int launch_adamw_mixed(float* p, void* g, float* m, float* v, void* plp, int64_t n, int decay_on, const float* hp,
+                       const int* step, const float* state, hipStream_t stream) {
+  if (n & 3) return 1;
+  const bool aligned = ((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)plp) % 16 == 0;
+  if (g_adamw_wide && (n & 7) == 0 && aligned) {
+    const int64_t n8 = n >> 3;
+    const dim3 grid(grid_for(n8, g_adamw_grid_cap));
+    if (state != nullptr)
+      hipLaunchKernelGGL((g_adamw_wide == 2 ? adamw_mixed8_kernel<false, true, const float*>
+                                            : adamw_mixed8_kernel<true, true, const float*>), grid,
+                         dim3(kBlock), 0, stream, (f32x4v*)p, (u16x8v*)g, (f32x4v*)m, (f32x4v*)v, (u16x8v*)plp, n8,
+                         decay_on, hp, step, state);
+    else
+      hipLaunchKernelGGL((g_adamw_wide == 2 ? adamw_mixed8_kernel<false, false> : adamw_mixed8_kernel<true, false>), grid,
+                         dim3(kBlock), 0, stream, (f32x4v*)p, (u16x8v*)g, (f32x4v*)m, (f32x4v*)v, (u16x8v*)plp, n8,
+                         decay_on, hp, step);
+    return (int)hipGetLastError();
+  }
+  const int64_t nv = n >> 2;
+  const dim3 grid(grid_for(nv, g_adamw_grid_cap));
+  if (state != nullptr)
+    hipLaunchKernelGGL((adamw_mixed_kernel<true, const float*>), grid, dim3(kBlock), 0, stream, (float4*)p, (u16x4*)g, (float4*)m,
+                       (float4*)v, (u16x4*)plp, nv, decay_on, hp, step, state);
+  else
+    hipLaunchKernelGGL(adamw_mixed_kernel<false>, grid, dim3(kBlock), 0, stream, (float4*)p, (u16x4*)g, (float4*)m,
+                       (float4*)v, (u16x4*)plp, nv, decay_on, hp, step);
+  return (int)hipGetLastError();
+}
+
+}  // namespace
+
+PLX_API int plx_sgd_flat(float* p, float* g, float* m, int64_t n, int64_t n_decay, const float* hp,
+                         const int* first_step, hipStream_t stream) {
+  return launch_sgd_flat(p, g, m, n, n_decay, hp, first_step, nullptr, stream);
+}
+
+PLX_API int plx_sgd_flat_clip(float* p, float* g, float* m, int64_t n, int64_t n_decay, const float* hp,
+                              const int* first_step, const float* state, hipStream_t stream) {
+  if (state == nullptr) return 1;
+  return launch_sgd_flat(p, g, m, n, n_decay, hp, first_step, state, stream);
 }
 
 PLX_API int plx_adamw_flat(float* p, float* g, float* m, float* v, int64_t n, int64_t n_decay, const float* hp,
                            const int* step, hipStream_t stream) {
-  if ((n & 3) || (n_decay & 3)) return 1;
-  const int64_t nv = n >> 2;
-  hipLaunchKernelGGL(adamw_flat_kernel, dim3(grid_for(nv, g_adamw_grid_cap)), dim3(kBlock), 0, stream, (float4*)p, (float4*)g,
-                     (float4*)m, (float4*)v, nv, n_decay >> 2, hp, step);
+  return launch_adamw_flat(p, g, m, v, n, n_decay, hp, step, nullptr, stream);
+}
+
+PLX_API int plx_adamw_flat_clip(float* p, float* g, float* m, float* v, int64_t n, int64_t n_decay, const float* hp,
+                                const int* step, const float* state, hipStream_t stream) {
+  if (state == nullptr) return 1;
+  return launch_adamw_flat(p, g, m, v, n, n_decay, hp, step, state, stream);
+}
+
+// Number of partial slots a range of n elements uses: a function of n alone.
+PLX_API int plx_gradnorm_blocks(int64_t n) { return gradnorm_blocks(n < 0 ? 0 : n); }
+
+// partials[0 .. plx_gradnorm_blocks(n)) = per-workgroup sums of squares of g[0 .. n) (fp32, or bf16 when is_bf16).
+// n % 4 == 0; g is 16-B aligned (fp32) or 8-B aligned (bf16).
+PLX_API int plx_gradnorm_partials(const void* g, int is_bf16, int64_t n, float* partials, hipStream_t stream) {
+  if (n < 0 || (n & 3) || g == nullptr || partials == nullptr) return 1;
+  const int grid = gradnorm_blocks(n);
+  if (!is_bf16) {
+    if ((uintptr_t)g % 16) return 1;
+    hipLaunchKernelGGL(gradnorm_f32_kernel, dim3(grid), dim3(kBlock), 0, stream, (const float4*)g, n >> 2, partials);
+    return (int)hipGetLastError();
+  }
+  if ((uintptr_t)g % 8) return 1;
+  const int head = (n > 0 && (uintptr_t)g % 16) ? 4 : 0;
+  const int64_t rest = n - head;
+  hipLaunchKernelGGL(gradnorm_bf16_kernel, dim3(grid), dim3(kBlock), 0, stream, (const unsigned short*)g, head,
+                     rest >> 3, (int)(rest & 7), partials);
+  return (int)hipGetLastError();
+}
+
+PLX_API int plx_gradnorm_finalize(const float* partials, int n_partials, const float* hp, float* state,
+                                  hipStream_t stream) {
+  if (n_partials < 0 || partials == nullptr || hp == nullptr || state == nullptr) return 1;
+  hipLaunchKernelGGL(gradnorm_finalize_kernel, dim3(1), dim3(kBlock), 0, stream, partials, n_partials, hp, state);
   return (int)hipGetLastError();
 }
 
@@ -433,18 +719,13 @@ PLX_API void plx_set_adamw_grid_cap(int blocks) { g_adamw_grid_cap = blocks < 1 
 
 PLX_API int plx_adamw_mixed(float* p, void* g, float* m, float* v, void* plp, int64_t n, int decay_on,
                             const float* hp, const int* step, hipStream_t stream) {
-  if (n & 3) return 1;
-  const bool aligned = ((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)plp) % 16 == 0;
-  if (g_adamw_wide && (n & 7) == 0 && aligned) {
-    const int64_t n8 = n >> 3;
-    hipLaunchKernelGGL(g_adamw_wide == 2 ? adamw_mixed8_kernel<false> : adamw_mixed8_kernel<true>, dim3(grid_for(n8, g_adamw_grid_cap)), dim3(kBlock), 0, stream,
-                       (f32x4v*)p, (u16x8v*)g, (f32x4v*)m, (f32x4v*)v, (u16x8v*)plp, n8, decay_on, hp, step);
-    return (int)hipGetLastError();
-  }
-  const int64_t nv = n >> 2;
-  hipLaunchKernelGGL(adamw_mixed_kernel, dim3(grid_for(nv, g_adamw_grid_cap)), dim3(kBlock), 0, stream, (float4*)p, (u16x4*)g,
-                     (float4*)m, (float4*)v, (u16x4*)plp, nv, decay_on, hp, step);
-  return (int)hipGetLastError();
+  return launch_adamw_mixed(p, g, m, v, plp, n, decay_on, hp, step, nullptr, stream);
+}
+
+PLX_API int plx_adamw_mixed_clip(float* p, void* g, float* m, float* v, void* plp, int64_t n, int decay_on,
+                                 const float* hp, const int* step, const float* state, hipStream_t stream) {
+  if (state == nullptr) return 1;
+  return launch_adamw_mixed(p, g, m, v, plp, n, decay_on, hp, step, state, stream);
 }
 
 PLX_API int plx_cast_lp(const float* p, void* plp, int64_t n, hipStream_t stream) {

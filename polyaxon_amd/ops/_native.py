@@ -209,6 +209,12 @@ SIGNATURES: Dict[str, Dict[str, list]] = {
         "plx_sgd_flat": [_P, _P, _P, _L, _L, _P, _P, _P],
         "plx_adamw_flat": [_P, _P, _P, _P, _L, _L, _P, _P, _P],
         "plx_adamw_mixed": [_P, _P, _P, _P, _P, _L, _I, _P, _P, _P],
+        "plx_sgd_flat_clip": [_P, _P, _P, _L, _L, _P, _P, _P, _P],
+        "plx_adamw_flat_clip": [_P, _P, _P, _P, _L, _L, _P, _P, _P, _P],
+        "plx_adamw_mixed_clip": [_P, _P, _P, _P, _P, _L, _I, _P, _P, _P, _P],
+        "plx_gradnorm_blocks": [_L],
+        "plx_gradnorm_partials": [_P, _I, _L, _P, _P],
+        "plx_gradnorm_finalize": [_P, _I, _P, _P, _P],
         "plx_cast_lp": [_P, _P, _L, _P],
         "plx_init_flat": [_P, _P, _P, _P, _I, _P, _P, _U64, _P],
         "plx_zero_flat": [_P, _L, _P],

@@ -137,6 +137,10 @@ class FlatDDP:
         step.  ``shard_optimizer``: ZeRO-1 over the optimizer's state (see the module docstring)."""
         if shard_optimizer and optimizer is None:
             raise ValueError("shard_optimizer needs the optimizer that runs inside the backward")
+        if optimizer is not None and getattr(optimizer, "clipping", False):
+            # global-norm clipping needs the whole (reduced) gradient before any update
+            raise ValueError("an optimizer built with max_grad_norm cannot update per bucket inside the backward "
+                             "(FlatDDP(optimizer=...), ZeRO-1): use plain FlatDDP and step_() after finish()")
         self.flat = flat
         self.opt = optimizer
         if optimizer is not None:

@@ -51,9 +51,12 @@ class ResidentTrialExecutor:
                  loss_fn: Optional[Callable] = None, optimizer: str = "sgd", use_graph: bool = True,
                  amp_dtype: Optional[torch.dtype] = torch.bfloat16, channels_last: bool = True,
                  ring_size: int = 4096, init_spec: Optional[Callable] = None,
-                 lp_dtype: Optional[torch.dtype] = None):
+                 lp_dtype: Optional[torch.dtype] = None, clip_grad: bool = False):
         """``lp_dtype`` (the language models, GPU): the model computes from bf16 weights with bf16 gradients and the
-        optimizer keeps the fp32 master (ops/flat.py lp mode); every re-init / restore refreshes the bf16 copy."""
+        optimizer keeps the fp32 master (ops/flat.py lp mode); every re-init / restore refreshes the bf16 copy.
+        ``clip_grad``: global-norm gradient clipping (ops/optim.py) with ``max_grad_norm`` as one more device
+        hyper-parameter: enabled with no limit (0) until a trial sets one, so the same captured step serves every
+        threshold."""
         self.device = torch.device(device)
         self.is_cuda = self.device.type == "cuda"
         if channels_last:
@@ -64,10 +67,11 @@ class ResidentTrialExecutor:
         self.flat.enable_direct_grads(True)  # native ops accumulate weight grads straight into flat.grads
         self._flatten_buffers()
         self.step = torch.zeros(1, dtype=torch.int32, device=self.device)
+        clip = 0.0 if clip_grad else None
         if optimizer == "sgd":
-            self.opt = FusedSGD(self.flat, step_counter=self.step)
+            self.opt = FusedSGD(self.flat, step_counter=self.step, max_grad_norm=clip)
         elif optimizer == "adamw":
-            self.opt = FusedAdamW(self.flat, step_counter=self.step)
+            self.opt = FusedAdamW(self.flat, step_counter=self.step, max_grad_norm=clip)
         else:
             raise ValueError(f"unknown optimizer {optimizer!r}")
         # default: cross entropy of the fp32-cast logits; on the GPU in one fused HIP kernel each way (ops/lm.py
@@ -291,6 +295,14 @@ class ResidentTrialExecutor:
 
     def set_hparams(self, **hp) -> None:
         self.opt.set_hparams(**{k: v for k, v in hp.items() if k in self.opt.HP})
+
+    def grad_norm(self) -> torch.Tensor:
+        """``clip_grad``: the last step's global gradient norm before clipping, a 0-dim device view (no sync)."""
+        return self.opt.grad_norm()
+
+    def clip_stats(self) -> Dict[str, float]:
+        """``clip_grad``: host floats {grad_norm, scale, skipped} of the last step; synchronises."""
+        return self.opt.clip_stats()
 
     def run(self, n_steps: int) -> None:
         for _ in range(n_steps):

@@ -9,6 +9,9 @@ trials (hyper-parameters, random init seed, Hyperband resource) is device data t
 
 Registry: ``resnet50`` (BASELINE.json config 3), ``resnet_tiny`` (same code path, CPU-test sized), ``mlp``
 (config 2), ``gpt2`` (config 4's GPT-2 125M trial), ``gpt2_tiny`` (same code path, CPU-test sized).  ``module:callable`` names any user factory with the same signature ``(params, device) -> TrialProgram``.
+
+Every built-in program takes ``params: {clip_grad: true}``: global-norm gradient clipping in the step, with
+``max_grad_norm`` as one more per-trial hyper-parameter (device data like the rest; 0 = no limit).
 """
 from __future__ import annotations
 
@@ -48,6 +51,19 @@ class TrialProgram:
             torch.cuda.synchronize(ex.device)
 
 
+def _clip_grad(params: Dict[str, Any]) -> bool:
+    return bool(params.get("clip_grad", False))
+
+
+def _with_clip(prog: TrialProgram, clip: bool) -> TrialProgram:
+    """``clip_grad`` programs understand ``max_grad_norm`` and warm up with a limit set."""
+    if clip:
+        prog.hp_keys = prog.hp_keys + ("max_grad_norm",)
+        prog.info["warm_hparams"] = {**prog.info.get("warm_hparams", {}), "max_grad_norm": 1.0}
+        prog.info["clip_grad"] = True
+    return prog
+
+
 def _resnet(params: Dict[str, Any], device, tiny: bool) -> TrialProgram:
     import torch
 
@@ -64,13 +80,16 @@ def _resnet(params: Dict[str, Any], device, tiny: bool) -> TrialProgram:
                            grid=int(params.get("grid", 4 if tiny else 7)), signal=float(params.get("signal", 0.5)),
                            seed=int(params.get("data_seed", 0)))
     model = resnet18ish(num_classes=classes) if tiny else resnet50(num_classes=classes)
-    ex = ResidentTrialExecutor(model, data, dev, optimizer="sgd", use_graph=bool(params.get("graph", False)))
-    return TrialProgram(ex, unit_steps=int(params.get("unit_steps", 1 if tiny else 4)),
-                        window=int(params.get("window", 4)), hp_keys=("lr", "momentum", "weight_decay", "nesterov"),
-                        info={"model": "resnet18ish" if tiny else "resnet50", "batch": batch, "image": image,
-                              "classes": classes, "data": "synthetic, fresh per step (ops/synth.py)",
-                              "warm_hparams": {"lr": 0.01, "momentum": 0.9, "weight_decay": 1e-4},
-                              "images_per_step": batch})
+    clip = _clip_grad(params)
+    ex = ResidentTrialExecutor(model, data, dev, optimizer="sgd", use_graph=bool(params.get("graph", False)),
+                               clip_grad=clip)
+    return _with_clip(TrialProgram(
+        ex, unit_steps=int(params.get("unit_steps", 1 if tiny else 4)),
+        window=int(params.get("window", 4)), hp_keys=("lr", "momentum", "weight_decay", "nesterov"),
+        info={"model": "resnet18ish" if tiny else "resnet50", "batch": batch, "image": image,
+              "classes": classes, "data": "synthetic, fresh per step (ops/synth.py)",
+              "warm_hparams": {"lr": 0.01, "momentum": 0.9, "weight_decay": 1e-4},
+              "images_per_step": batch}), clip)
 
 
 def _mlp(params: Dict[str, Any], device) -> TrialProgram:
@@ -84,11 +103,14 @@ def _mlp(params: Dict[str, Any], device) -> TrialProgram:
     g = torch.Generator().manual_seed(int(params.get("data_seed", 0)))
     x = torch.randn(bs, 784, generator=g)
     y = (x @ torch.randn(784, 10, generator=g)).argmax(1)
-    ex = ResidentTrialExecutor(MLP(), (x, y), dev, optimizer="sgd", use_graph=dev.type == "cuda", channels_last=False)
-    return TrialProgram(ex, unit_steps=int(params.get("unit_steps", 10)), window=int(params.get("window", 4)),
-                        hp_keys=("lr", "momentum", "weight_decay"),
-                        info={"model": "mlp", "batch": bs, "warm_hparams": {"lr": 0.01, "momentum": 0.9},
-                              "images_per_step": bs})
+    clip = _clip_grad(params)
+    ex = ResidentTrialExecutor(MLP(), (x, y), dev, optimizer="sgd", use_graph=dev.type == "cuda", channels_last=False,
+                               clip_grad=clip)
+    return _with_clip(TrialProgram(
+        ex, unit_steps=int(params.get("unit_steps", 10)), window=int(params.get("window", 4)),
+        hp_keys=("lr", "momentum", "weight_decay"),
+        info={"model": "mlp", "batch": bs, "warm_hparams": {"lr": 0.01, "momentum": 0.9},
+              "images_per_step": bs}), clip)
 
 
 def _gpt2(params: Dict[str, Any], device, tiny: bool) -> TrialProgram:
@@ -121,19 +143,21 @@ def _gpt2(params: Dict[str, Any], device, tiny: bool) -> TrialProgram:
             model = Transformer(cfg)
     else:
         model = Transformer(cfg)
+    clip = _clip_grad(params)
     ex = ResidentTrialExecutor(model, data, dev, loss_fn=lm_loss, optimizer="adamw",
                                use_graph=bool(params.get("graph", False)), channels_last=False,
-                               lp_dtype=torch.bfloat16)
-    return TrialProgram(ex, unit_steps=int(params.get("unit_steps", 4 if tiny else 10)),
-                        window=int(params.get("window", 4)),
-                        hp_keys=("lr", "beta1", "beta2", "eps", "weight_decay"),
-                        info={"model": "gpt2_tiny" if tiny else "gpt2_125m", "batch": batch, "seq": seq,
-                              "vocab": cfg.vocab_size, "data": f"synthetic {task} task, fresh per step (ops/synth.py)",
-                              "warm_hparams": {"lr": 3e-4, "beta1": 0.9, "beta2": 0.95, "eps": 1e-8,
-                                               "weight_decay": 0.1},
-                              "tokens_per_step": batch * seq, "floor_loss": data.floor_loss,
-                              "unigram_loss": data.unigram_loss, "chance_loss": data.chance_loss,
-                              "active_vocab": data.active_vocab})
+                               lp_dtype=torch.bfloat16, clip_grad=clip)
+    return _with_clip(TrialProgram(
+        ex, unit_steps=int(params.get("unit_steps", 4 if tiny else 10)),
+        window=int(params.get("window", 4)),
+        hp_keys=("lr", "beta1", "beta2", "eps", "weight_decay"),
+        info={"model": "gpt2_tiny" if tiny else "gpt2_125m", "batch": batch, "seq": seq,
+              "vocab": cfg.vocab_size, "data": f"synthetic {task} task, fresh per step (ops/synth.py)",
+              "warm_hparams": {"lr": 3e-4, "beta1": 0.9, "beta2": 0.95, "eps": 1e-8,
+                               "weight_decay": 0.1},
+              "tokens_per_step": batch * seq, "floor_loss": data.floor_loss,
+              "unigram_loss": data.unigram_loss, "chance_loss": data.chance_loss,
+              "active_vocab": data.active_vocab}), clip)
 
 
 PROGRAMS: Dict[str, Callable[[Dict[str, Any], Any], TrialProgram]] = {

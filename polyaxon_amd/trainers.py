@@ -39,6 +39,9 @@ def _parser(name: str) -> argparse.ArgumentParser:
     ap.add_argument("--lr", type=float, default=1e-3)
     ap.add_argument("--weight_decay", type=float, default=0.0)
     ap.add_argument("--momentum", type=float, default=0.9)
+    ap.add_argument("--max_grad_norm", type=float, default=0.0,
+                    help="clip the global gradient norm to this value in the fused optimizer step (lm, resnet); "
+                         "0 = off: the optimizer is built without clipping")
     ap.add_argument("--bs", type=int, default=64)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--log_every", type=int, default=10)
@@ -139,7 +142,8 @@ def train_resnet(argv=None) -> float:
     x = torch.randn(args.bs, 3, args.image, args.image, generator=g).to(torch.bfloat16)
     x = x.contiguous(memory_format=torch.channels_last)
     y = torch.randint(0, 1000, (args.bs,), generator=g)
-    ex = ResidentTrialExecutor(resnet50(), (x, y), dev, use_graph=False)
+    clip = args.max_grad_norm > 0
+    ex = ResidentTrialExecutor(resnet50(), (x, y), dev, use_graph=False, clip_grad=clip)
     ckpt = _ckpt_path() if args.ckpt else None
     done_units = 0
     ex.reset(seed=args.seed)
@@ -150,7 +154,9 @@ def train_resnet(argv=None) -> float:
         ex.buffers.copy_(st["buffers"])
         ex.step.fill_(int(st["step"]))
         done_units = int(st["units"])
-    ex.set_hparams(lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay)
+    # (the executor passes on only what its optimizer knows: max_grad_norm exists when clipping is on)
+    ex.set_hparams(lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay,
+                   max_grad_norm=args.max_grad_norm)
     ex.run(max(0, args.units - done_units) * args.unit_steps)
     out = torch.full((1,), float("nan"), device=dev)
     ex.commit(out, 0, window=4)
@@ -198,6 +204,11 @@ def train_lm(argv=None) -> float:
                     help="ZeRO-1: reduce-scatter each gradient bucket, AdamW on this rank's 1/W slice inside the "
                          "backward, all-gather the bf16 weights (parallel/ddp.py); also PLX_ZERO1=1")
     args = _parse(ap, argv)
+    clip = args.max_grad_norm > 0
+    if clip and (args.zero1 or os.environ.get("PLX_ZERO1", "0") == "1"
+                 or os.environ.get("PLX_OPT_IN_BACKWARD", "0") == "1"):
+        ap.error("--max_grad_norm needs the whole gradient before any update: it cannot be combined with --zero1 / "
+                 "PLX_ZERO1=1 / PLX_OPT_IN_BACKWARD=1 (AdamW per bucket inside the backward)")
     # the process group is the gloo rendezvous; every device collective of the trial (gradient buckets, ZeRO-1,
     # the parameter broadcast, the metric mean) runs on ONE framework RCCL communicator (parallel/comm.py)
     cuda = not args.cpu and torch.cuda.is_available()
@@ -226,7 +237,8 @@ def train_lm(argv=None) -> float:
     if lp is not None:
         flat.enable_direct_grads(True)  # weight-gradient GEMMs write into the flat bf16 grads (ops/lm.py)
     step = torch.zeros(1, dtype=torch.int32, device=dev)
-    opt = FusedAdamW(flat, lr=args.lr, betas=(0.9, args.beta2), weight_decay=args.weight_decay, step_counter=step)
+    opt = FusedAdamW(flat, lr=args.lr, betas=(0.9, args.beta2), weight_decay=args.weight_decay, step_counter=step,
+                     max_grad_norm=args.max_grad_norm if clip else None)
     # PLX_OPT_IN_BACKWARD=1: the AdamW update of each gradient bucket runs inside the backward as the bucket completes
     # (parallel/ddp.py).  Off by default: bitwise the same trajectory, but on one MI355X the HBM-bound update only
     # moved time from itself to the backward's memory-bound kernels (Llama-3 8B 18.17k vs 18.03k tokens/s with a
@@ -276,7 +288,9 @@ def train_lm(argv=None) -> float:
         if (it + 1) % args.log_every == 0 or it == args.steps - 1:
             loss_mean = metrics.mean(loss)  # every rank joins the collective; rank 0 logs it
             if xp is not None and (it + 1) % args.log_every == 0:
-                xp.log_metrics(step=it + 1, loss=loss_mean[0])
+                # the norm of the averaged gradients is the same on every rank: no reduction of its own
+                extra = {"grad_norm": opt.grad_norm().clone()} if clip else {}
+                xp.log_metrics(step=it + 1, loss=loss_mean[0], **extra)
             if it == args.steps - 1:
                 loss_val = float(loss_mean[0])
     t_host = time.time() - t0  # the host has queued every step (a host time ~ dt: the GPU waited for launches)
@@ -291,7 +305,11 @@ def train_lm(argv=None) -> float:
         from polyaxon_amd.ops import gemm as _gemm
 
         dec = _gemm.decisions()
-        print(json.dumps({"loss": loss_val, "tokens_per_s": round(tok_s, 1), "world": info["world"],
+        clip_out = {}
+        if clip:
+            cs = opt.clip_stats()
+            clip_out = {"grad_norm": cs["grad_norm"], "skipped_steps": int(cs["skipped"])}
+        print(json.dumps({"loss": loss_val, "tokens_per_s": round(tok_s, 1), "world": info["world"], **clip_out,
                           "ms_per_step": round(dt / max(1, args.steps - skip) * 1e3, 3),
                           "host_ms_per_step": round(t_host / max(1, args.steps - skip) * 1e3, 3),
                           "world1_collectives": args.world1_collectives if force else "", "zero1": zero1, "bucket_launches": ddp.launched,
