@@ -964,6 +964,18 @@ PLX_API int plx_bn_apply(const void* x, const void* res, void* y, int64_t M, int
   return (int)hipGetLastError();
 }
 
+// The training forward's apply + residual + ReLU pass on its own (bn_apply_kernel<true, true>): y and the 1-bit mask
+// from scale_bias, with res_sb (nullable [2C]) the residual's deferred affine.  It fills a block output whose apply was
+// deferred to a consumer that did not take it (ops/conv1x1.py PendingApply), and is what plx_gemm_nt_bnapply is
+// tested against.
+PLX_API int plx_bn_apply_res_relu(const void* x, const void* res, void* y, int64_t M, int C, const float* scale_bias,
+                                  uint8_t* mask, const float* res_sb, hipStream_t stream) {
+  Plan p;
+  if (!plan_for(M, C, &p) || M < 1 || res == nullptr || mask == nullptr) return 1;
+  launch_apply(stream, M * p.G, p.G, x, res, y, scale_bias, scale_bias + C, 1, mask, res_sb);
+  return (int)hipGetLastError();
+}
+
 // mask: the ReLU bit mask written by the forward (required when relu); accumulate: dgamma/dbeta += (else =)
 // Row blocks of the dx pass = the nblk of the residual-BatchNorm partials it writes (ResBn, plx_bn_backward*).
 PLX_API int plx_bn_dx_blocks(int64_t M, int C) {

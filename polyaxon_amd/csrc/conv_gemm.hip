@@ -4,6 +4,7 @@
 //   forward      y[M][Cout]  = x[M][Cin]   . W[Cout][Cin]^T       -> plx_gemm_nt   (A = x,  B = W)
 //   data grad    dx[M][Cin]  = dy[M][Cout] . Wt[Cin][Cout]^T      -> plx_gemm_nt   (A = dy, B = W^T)
 //                the same with dy = the dx of the BatchNorm behind the conv, formed in the kernel -> plx_gemm_nt_bndx
+//                the forward with x = relu(bn(y3) + residual) of the block before, formed in the kernel -> plx_gemm_nt_bnapply
 //   weight grad  dW[Cout][Cin] = sum_m dy[m][Cout]^T x[m][Cin]    -> plx_gemm_tn   (split over m, fp32 out)
 // plx_gemm_nt needs both operands K-contiguous (row-major [rows][K]); plx_gemm_tn reads both operands
 // row-major over the reduction index m and feeds the MFMA through ds_read_b64_tr_b16 transposed LDS reads.
@@ -120,6 +121,21 @@ struct BnDx {
     __bf16* dy;
 };
 
+// BatchNorm apply + residual add + ReLU produced inside the forward GEMM that consumes it (gemm_nt_kernel, BNAP).  The
+// GEMM's A operand is out = relu(x * scale[k] + bias[k] + (res * ra[k] + rb[k])) of a bottleneck's last BatchNorm with
+// raw input x (passed as the GEMM's A pointer) and residual res; (ra, rb) = rsb's two rows when the residual is the raw
+// input of a BatchNorm whose apply was deferred (BNAP 2), else (1, 0) (BNAP 1).  The kernel forms it on the global ->
+// LDS path with the expression and the single bf16 rounding of bn_apply_kernel<true, true> (csrc/bn_kernels.hip),
+// writes it to out and its sign bits to mask once (the shortcut, the weight gradient and the backward read them) and
+// feeds the rounded tile to the MFMAs.  x, res and out are dense [M][K]; mask has one bit per element.
+struct BnApply {
+    const __bf16* res;
+    const float* sb;       // fp32 [2][K]: scale | bias
+    const float* rsb;      // fp32 [2][K]: the residual's scale | bias (BNAP 2 only)
+    __bf16* out;
+    uint8_t* mask;
+};
+
 __device__ __forceinline__ void row_coords(int m, int Hr, int Wr, int& n, int& r, int& c) {
     const int q = m / Wr;
     c = m - q * Wr;
@@ -203,14 +219,20 @@ __device__ __forceinline__ int nt_swz(int row) { return (row >> 1) & 7; }
 // k+1 into registers before the MFMAs of stage k, transforms them afterwards and writes them into the other stage
 // buffer in the image the fragment reads expect; the tn == 0 block of a row panel also stores them to dy, after the
 // stage's barrier, so the stores have a whole stage to complete before the next vmcnt(0).
+// BNAP (dense forward, NBUF 2; 1 plain residual, 2 residual with its own scale/bias): the same recipe for the forward --
+// the A operand is a BatchNorm apply + residual + ReLU, produced here (BnApply) from x, the residual and the 8 channels'
+// scale/bias; the tn == 0 block stores the rounded chunks to out and one mask byte per chunk after the stage's barrier.
 template <int BM, int BN, int WGM, int WGN, int MODE, int MINB = 2, int NBUF = 2, bool BWD = false, int NTH = NTHREADS,
-          bool BNDX = false>
+          bool BNDX = false, int BNAP = 0>
 __global__ void __launch_bounds__(NTH, MINB)
 gemm_nt_kernel(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf16* __restrict__ C,
                int M, int N, int K, int lda, int ldb, int ldc, const __bf16* __restrict__ zero,
                float* __restrict__ stats, ConvGeom geo, const __bf16* __restrict__ D, int ldd, BnBwd bnr,
-               const uint8_t* __restrict__ dmask, BnDx bd) {
+               const uint8_t* __restrict__ dmask, BnDx bd, BnApply ba) {
     constexpr bool CONV = MODE == 1, STEM = MODE == 2;
+    constexpr bool PROD = BNDX || BNAP != 0;               // the kernel produces its A operand
+    static_assert(BNAP >= 0 && BNAP <= 2 && !(BNDX && BNAP != 0), "one producer mode");
+    static_assert(BNAP == 0 || (MODE == 0 && NBUF == 2 && !BWD && NTH == 256), "BNAP: dense double-buffered forward");
     static_assert(MODE >= 0 && MODE <= 2, "dense, gather or stem");
     static_assert(!BNDX || (MODE == 0 && NBUF == 2 && BWD && NTH == 256), "BNDX: dense double-buffered data gradient");
     constexpr int NW = NTH / 64;                           // waves
@@ -335,19 +357,21 @@ gemm_nt_kernel(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf1
         st = tap_inner ? st_i : st_m;
         sc = tap_inner ? sc_i : sc_m;
     };
-    // BNDX staging state.  Chunk i of this thread is row (i * NW + wave) * 8 + lane / 8, physical 16-B chunk lane % 8
+    // BNDX / BNAP staging state.  Chunk i of this thread is row (i * NW + wave) * 8 + lane / 8, physical 16-B chunk lane % 8
     // of the stage image, i.e. logical chunk lc = lane % 8 ^ nt_swz(row) -- the same for every i (rows step by 32), so
     // the thread keeps one 8-channel column and one set of coefficients per stage.  All of it moves through buffer
     // resources: one 32-bit byte offset per chunk serves g, x and dy (the stage's k0 rides in the scalar offset), and
-    // rows past M get the out-of-range offset -- their loads return zeros, their stores are dropped.
-    constexpr int XI = BNDX ? AI : 1;
+    // rows past M get the out-of-range offset -- their loads return zeros, their stores are dropped.  (BNAP: gq = x,
+    // xq = the residual, oq = out, mq = the mask bytes to store, four chunks' to a register, cf = scale | bias
+    // (| residual scale | bias).)
+    constexpr int XI = PROD ? AI : 1;
     uint32_t e_off[XI];                                     // byte offset of the chunk at k0 = 0 (M * K * 2 < 2^31)
     u32x4 gq[XI], xq[XI], oq[XI];
     uint32_t mq[XI];
-    u32x4 cf[6];                                            // A | B | D of the thread's 8 channels
+    u32x4 cf[BNAP == 2 ? 8 : 6];                            // A | B | D of the thread's 8 channels
     const int lc8 = (((lane & 7) ^ nt_swz(wave * 8 + (lane >> 3))) & 7) * 8;
     const bool dy_owner = tn == 0;                          // one block per row panel stores dy
-    if constexpr (BNDX) {
+    if constexpr (PROD) {
 #pragma unroll
         for (int i = 0; i < XI; ++i) {
             const int gm = m0 + (i * NW + wave) * 8 + (lane >> 3);
@@ -406,6 +430,79 @@ gemm_nt_kernel(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf1
 #pragma unroll
         for (int i = 0; i < XI; ++i) __builtin_amdgcn_raw_buffer_store_b128(oq[i], rd, (int)e_off[i], k0 * 2, 0);
     };
+    // BNAP: the same three steps for the forward's out = relu(bn(x) + residual)
+    auto load_ap = [&](int k0) {
+        if constexpr (BNAP != 0) {
+            const __amdgpu_buffer_rsrc_t rr = buf_rsrc(ba.res), rc = buf_rsrc(ba.sb);
+#pragma unroll
+            for (int i = 0; i < XI; ++i) {
+                gq[i] = __builtin_amdgcn_raw_buffer_load_b128(ra, (int)e_off[i], k0 * 2, 0);
+                xq[i] = __builtin_amdgcn_raw_buffer_load_b128(rr, (int)e_off[i], k0 * 2, 0);
+            }
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                cf[2 * r] = __builtin_amdgcn_raw_buffer_load_b128(rc, lc8 * 4, (r * K + k0) * 4, 0);
+                cf[2 * r + 1] = __builtin_amdgcn_raw_buffer_load_b128(rc, lc8 * 4 + 16, (r * K + k0) * 4, 0);
+            }
+            if constexpr (BNAP == 2) {
+                const __amdgpu_buffer_rsrc_t rs = buf_rsrc(ba.rsb);
+#pragma unroll
+                for (int r = 0; r < 2; ++r) {
+                    cf[4 + 2 * r] = __builtin_amdgcn_raw_buffer_load_b128(rs, lc8 * 4, (r * K + k0) * 4, 0);
+                    cf[5 + 2 * r] = __builtin_amdgcn_raw_buffer_load_b128(rs, lc8 * 4 + 16, (r * K + k0) * 4, 0);
+                }
+            }
+        }
+    };
+    auto xform_ap = [&](int buf) {                          // registers -> out chunks (oq), mask bytes (mq) -> stage image
+        if constexpr (BNAP != 0) {
+            char* base = smem + buf * STAGE;
+            const float* ca = (const float*)&cf[0];
+            const float* cb = (const float*)&cf[2];
+            const float* cra = (const float*)&cf[BNAP == 2 ? 4 : 0];
+            const float* crb = (const float*)&cf[BNAP == 2 ? 6 : 0];
+#pragma unroll
+            for (int i = 0; i < XI; ++i) {
+                const uint32_t* px = (const uint32_t*)&gq[i];
+                const uint32_t* pr = (const uint32_t*)&xq[i];
+                uint32_t* po = (uint32_t*)&oq[i];
+                uint32_t bits = 0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float x0 = __uint_as_float(px[j] << 16), x1 = __uint_as_float(px[j] & 0xffff0000u);
+                    const float r0 = __uint_as_float(pr[j] << 16), r1 = __uint_as_float(pr[j] & 0xffff0000u);
+                    const float ra0 = BNAP == 2 ? cra[2 * j] : 1.f, ra1 = BNAP == 2 ? cra[2 * j + 1] : 1.f;
+                    const float rb0 = BNAP == 2 ? crb[2 * j] : 0.f, rb1 = BNAP == 2 ? crb[2 * j + 1] : 0.f;
+                    float v0 = fmaf(x0, ca[2 * j], cb[2 * j]), v1 = fmaf(x1, ca[2 * j + 1], cb[2 * j + 1]);
+                    v0 += fmaf(r0, ra0, rb0);
+                    v1 += fmaf(r1, ra1, rb1);
+                    v0 = fmaxf(v0, 0.f);
+                    v1 = fmaxf(v1, 0.f);
+                    bits |= (uint32_t)(v0 > 0.f) << (2 * j) | (uint32_t)(v1 > 0.f) << (2 * j + 1);
+                    po[j] = pack_bf16x2(v0, v1);
+                }
+                mq[i >> 2] = (i & 3) == 0 ? bits : mq[i >> 2] | bits << (8 * (i & 3));
+                if (e_off[i] == OOB) oq[i] = u32x4{0u, 0u, 0u, 0u};
+                *(u32x4*)(base + (i * NW + wave) * 1024 + lane * 16) = oq[i];
+            }
+        }
+    };
+    auto store_ap = [&](int k0) {                           // byte (element offset / 8) of the mask
+        if constexpr (BNAP != 0) {
+            if (!dy_owner) return;
+            // the mask's range is OOB / 16 bytes (M * K / 8 < 2^27), so a chunk's byte offset / 16 serves as is and
+            // the out-of-range one stays out of range; formed from the stage's offset here, not held per chunk
+            const __amdgpu_buffer_rsrc_t ro = buf_rsrc(ba.out);
+            const __amdgpu_buffer_rsrc_t rm =
+                __builtin_amdgcn_make_buffer_rsrc(ba.mask, 0, (int)(OOB >> 4), 0x00020000);
+#pragma unroll
+            for (int i = 0; i < XI; ++i) {
+                __builtin_amdgcn_raw_buffer_store_b128(oq[i], ro, (int)e_off[i], k0 * 2, 0);
+                __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(mq[i >> 2] >> (8 * (i & 3))), rm,
+                                                     (int)((e_off[i] + (uint32_t)(k0 * 2)) >> 4), 0, 0);
+            }
+        }
+    };
     if constexpr (BNDX) {
         static_assert(!BNDX || NW == 4, "a thread's rows step by 32: one chunk column per thread");
         load_a(0);
@@ -414,6 +511,14 @@ gemm_nt_kernel(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf1
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         store_dy(0);
+    } else if constexpr (BNAP != 0) {
+        static_assert(BNAP == 0 || NW == 4, "a thread's rows step by 32: one chunk column per thread");
+        load_ap(0);
+        stage_b(0, 0, 0, 0);
+        xform_ap(0);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        store_ap(0);
     } else {
         stage(0, 0, 0, 0);
         advance();
@@ -428,13 +533,19 @@ gemm_nt_kernel(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf1
                 stage_b(cur ^ 1, (kt + 1) * BK, 0, 0);
             }
         }
-        if (!BNDX && NBUF == 1 && kt > 0) {                 // restage the single buffer (the loop's tail barrier
+        if constexpr (BNAP != 0) {
+            if (kt + 1 < nk) {
+                load_ap((kt + 1) * BK);
+                stage_b(cur ^ 1, (kt + 1) * BK, 0, 0);
+            }
+        }
+        if (!PROD && NBUF == 1 && kt > 0) {                 // restage the single buffer (the loop's tail barrier
             stage(0, kt * BK, st, sc);                      // retired its readers)
             advance();
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
         }
-        if (!BNDX && NBUF == 2 && kt + 1 < nk) {
+        if (!PROD && NBUF == 2 && kt + 1 < nk) {
             stage(cur ^ 1, (kt + 1) * BK, st, sc);
             advance();
         }
@@ -464,10 +575,16 @@ gemm_nt_kernel(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf1
         if constexpr (BNDX) {                               // the other buffer's readers retired at the last barrier
             if (kt + 1 < nk) xform_a(cur ^ 1);
         }
+        if constexpr (BNAP != 0) {
+            if (kt + 1 < nk) xform_ap(cur ^ 1);
+        }
         if (NBUF == 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         if constexpr (BNDX) {
             if (kt + 1 < nk) store_dy((kt + 1) * BK);
+        }
+        if constexpr (BNAP != 0) {
+            if (kt + 1 < nk) store_ap((kt + 1) * BK);
         }
     }
     // Epilogue through LDS (the k-loop's last barrier freed it): D[n][m] has column m = fr and rows
@@ -1220,7 +1337,7 @@ int launch_nt(const void* A, const void* B, void* C, int M, int N, int K, int ld
     auto k = bwd ? kb : kf;
     const int nwg = ((M + BM - 1) / BM) * (N / BN);
     hipLaunchKernelGGL(k, dim3(nwg), dim3(NTH), LDS, s, (const __bf16*)A, (const __bf16*)B, (__bf16*)C, M, N,
-                       K, lda, ldb, ldc, (const __bf16*)zero, stats, geo, (const __bf16*)D, ldd, bnr, dmask, BnDx{});
+                       K, lda, ldb, ldc, (const __bf16*)zero, stats, geo, (const __bf16*)D, ldd, bnr, dmask, BnDx{}, BnApply{});
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
@@ -1238,7 +1355,26 @@ int launch_nt_bndx(const void* g, const BnDx& bd, const void* B, void* C, int M,
     const int nwg = ((M + BM - 1) / BM) * (N / BN);
     hipLaunchKernelGGL(k, dim3(nwg), dim3(NTHREADS), LDS, s, (const __bf16*)g, (const __bf16*)B, (__bf16*)C, M, N, K, K,
                        ldb, ldc, (const __bf16*)nullptr, (float*)nullptr, ConvGeom{}, (const __bf16*)D, ldd, bnr, dmask,
-                       bd);
+                       bd, BnApply{});
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+// The forward GEMM that produces its A operand, a BatchNorm apply + residual + ReLU (BnApply), double-buffered at 2
+// blocks per CU.  x = the BatchNorm's raw input (the kernel's A pointer), dense like ba.res and ba.out (ld = K).  The
+// tiles are plx_gemm_nt's, so y and the stats partials keep their values, layout and summation order.
+template <int BM, int BN, int WGM, int WGN, int BNAP>
+int launch_nt_bnapply(const void* x, const BnApply& ba, const void* B, void* C, int M, int N, int K, int ldb, int ldc,
+                      float* stats, hipStream_t s) {
+    constexpr int TILE = BM * (BN * 2 + 16), RED = NTHREADS * 17 * 4;
+    constexpr int LDS = 2 * (BM + BN) * BK * 2;
+    static_assert(TILE <= LDS && RED <= LDS && LDS <= 80 * 1024, "epilogue staging fits; 2 blocks per CU");
+    auto k = gemm_nt_kernel<BM, BN, WGM, WGN, 0, 2, 2, false, NTHREADS, false, BNAP>;
+    static int attr = set_lds(k, LDS);
+    if (attr) return attr;
+    const int nwg = ((M + BM - 1) / BM) * (N / BN);
+    hipLaunchKernelGGL(k, dim3(nwg), dim3(NTHREADS), LDS, s, (const __bf16*)x, (const __bf16*)B, (__bf16*)C, M, N, K, K,
+                       ldb, ldc, (const __bf16*)nullptr, stats, ConvGeom{}, (const __bf16*)nullptr, 0, BnBwd{},
+                       (const uint8_t*)nullptr, BnDx{}, ba);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
@@ -1530,6 +1666,30 @@ int plx_gemm_nt_bndx(const void* g, const void* x, const uint8_t* mask, const fl
     hipStream_t s = (hipStream_t)stream;
     if (N % 128 == 0) return launch_nt_bndx<128, 128, 2, 2>(g, bd, Wt, C, M, N, K, ldb, ldc, s, D, ldd, b, dmask);
     return launch_nt_bndx<256, 64, 4, 1>(g, bd, Wt, C, M, N, K, ldb, ldc, s, D, ldd, b, dmask);
+}
+
+// Forward of a 1x1 convolution whose input is the block output relu(bn(x) + residual) of the bottleneck before it,
+// produced in the kernel:
+//   out[M][K] = bf16(max(x * sb[k] + sb[K + k] + (res * ra[k] + rb[k]), 0)),  mask bit = (that sum > 0)
+//   C[M][N]   = out . W[N][K]^T  (+ the channel-stats partials of plx_gemm_nt)
+// (ra, rb) = (rsb[k], rsb[K + k]) with rsb, else (1, 0): out and mask are bit-identical to bn_apply_kernel<true, true>.
+// x, res, out: dense bf16 [M][K]; mask: uint8 [M * K / 8]; sb, rsb (nullable): fp32 [2][K].  The tiles are those of
+// plx_gemm_nt (plx_gemm_nt_rows_per_block), so C and stats are bit-identical to the apply pass + plx_gemm_nt.  With
+// several N tiles per row panel every tile's block repeats the transform and only the first stores out and mask; the
+// Python side only sends N <= 128 here (models/resnet.py).
+int plx_gemm_nt_bnapply(const void* x, const void* res, const float* sb, const float* rsb, void* out, uint8_t* mask,
+                        const void* W, void* C, int M, int N, int K, int ldb, int ldc, float* stats, void* stream) {
+    if (M <= 0 || N % 64 || K % BK || ldb % 8 || ldc % 8) return -1;
+    if (x == nullptr || res == nullptr || sb == nullptr || out == nullptr || mask == nullptr || out == x || out == res)
+        return -1;
+    if ((long)M * K >= (1l << 30)) return -1;             // 32-bit byte offsets into x / res / out
+    const BnApply ba{(const __bf16*)res, sb, rsb, (__bf16*)out, mask};
+    hipStream_t s = (hipStream_t)stream;
+    if (N % 128 == 0)
+        return rsb != nullptr ? launch_nt_bnapply<128, 128, 2, 2, 2>(x, ba, W, C, M, N, K, ldb, ldc, stats, s)
+                              : launch_nt_bnapply<128, 128, 2, 2, 1>(x, ba, W, C, M, N, K, ldb, ldc, stats, s);
+    return rsb != nullptr ? launch_nt_bnapply<256, 64, 4, 1, 2>(x, ba, W, C, M, N, K, ldb, ldc, stats, s)
+                          : launch_nt_bnapply<256, 64, 4, 1, 1>(x, ba, W, C, M, N, K, ldb, ldc, stats, s);
 }
 
 // diagnostics: K slices (fp32 slabs) the weight-gradient plan of this problem uses (v2: wgrad_kernel's plan)

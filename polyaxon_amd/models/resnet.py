@@ -13,6 +13,7 @@ from typing import List, Optional, Type
 import torch
 import torch.nn as nn
 
+from polyaxon_amd.ops import conv1x1 as _c1
 from polyaxon_amd.ops.conv1x1 import Conv1x1, GradMailbox
 from polyaxon_amd.ops.conv import Conv3x3, ConvKxK
 from polyaxon_amd.ops.norm import BatchNormAct
@@ -37,7 +38,9 @@ class Bottleneck(nn.Module):
         self.bn3 = BatchNormAct(out_ch, act=True, fused=fused, residual=True)
         self.downsample = downsample
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, defer_out: bool = False) -> torch.Tensor:
+        """``defer_out`` (set by :meth:`ResNet.forward_features`, which knows the successor): bn3 leaves its apply +
+        residual + ReLU pass to the forward GEMM of the next block's conv1 (ops.conv1x1.PendingApply)."""
         train = self.training and torch.is_grad_enabled() and x.requires_grad
         box = GradMailbox() if train else None
         if self.downsample is None:
@@ -45,15 +48,32 @@ class Bottleneck(nn.Module):
             # so conv1's dgrad is x's whole gradient and serves the previous block's bn3 its backward partials
             out = self.bn1(self.conv1(x, grad_box=box, bn_link=True))
             out = self.bn2(self.conv2(out, bn_link=True))
-            return self.bn3(self.conv3(out, bn_link=True), x, residual_grad_box=box)
+            return self.bn3(self.conv3(out, bn_link=True), x, residual_grad_box=box, defer_res_relu=defer_out)
         # downsampling block: conv1's data gradient is deferred into the downsample conv's dgrad epilogue, and the
         # downsample BatchNorm's output feeds only bn3, so bn3's dx pass reduces that BatchNorm's backward partials
         identity = self.downsample(x, grad_box=box)
         out = self.bn1(self.conv1(x, grad_sink=box, bn_link=True))
         out = self.bn2(self.conv2(out, bn_link=True))
-        return self.bn3(self.conv3(out, bn_link=True), identity, residual_link=True)
+        return self.bn3(self.conv3(out, bn_link=True), identity, residual_link=True, defer_res_relu=defer_out)
+
+    def takes_pending(self, x: torch.Tensor) -> bool:
+        """Can this block's conv1 produce its own input, the block output before it (of ``x``'s device, dtype class
+        and batch), inside its forward GEMM?  An identity block only: in a downsampling block the strided downsample
+        conv reads the input before conv1 runs, and the GradMailbox ordering forbids swapping them."""
+        c = self.conv1
+        return (self.downsample is None and self.training and c.native and _c1.supported(x, c)
+                and _c1.bn_apply_sink_ok(c.in_channels, c.out_channels))
 
 
+def run_blocks(blocks, x: torch.Tensor) -> torch.Tensor:
+    """A stage's bottlenecks in sequence.  The loop knows each block's successor, so it is the one to decide: a block
+    whose successor's conv1 can form the block output in its own forward GEMM (:meth:`Bottleneck.takes_pending`)
+    leaves bn3's apply + residual + ReLU pass to it; the last block of a stage always writes its output."""
+    blocks = list(blocks)
+    for i, blk in enumerate(blocks):
+        nxt = blocks[i + 1] if i + 1 < len(blocks) else None
+        x = blk(x, defer_out=blk.training and nxt is not None and nxt.takes_pending(x))
+    return x
 
 
 class Downsample(nn.Module):
@@ -134,7 +154,9 @@ class ResNet(nn.Module):
         x = self.stem(x)
         # BN + ReLU + max-pool fused (ops/stem.py): the 112x112 BatchNorm output is never materialised
         x = stem_bn_relu_pool(x, self.stem_bn, self.pool)
-        return self.stages(x)
+        for stage in self.stages:
+            x = run_blocks(stage, x)
+        return x
 
     def forward_head(self, x: torch.Tensor) -> torch.Tensor:
         """Global average pool (NHWC kernel, ops/pool.py) + fc."""

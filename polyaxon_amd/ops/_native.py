@@ -228,6 +228,7 @@ SIGNATURES: Dict[str, Dict[str, list]] = {
         "plx_bn_workspace": [_L, _I],
         "plx_bn_forward": [_P, _P, _P, _L, _I, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P],
         "plx_bn_apply": [_P, _P, _P, _L, _I, _P, _I, _P],
+        "plx_bn_apply_res_relu": [_P, _P, _P, _L, _I, _P, _P, _P, _P],
         "plx_bn_l2_workspace": [_I, _I],
         "plx_bn_forward_from_partials": [_P, _P, _P, _L, _I, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P, _I, _P, _P,
                                          _I, _P, _P, _P],
@@ -268,6 +269,7 @@ SIGNATURES: Dict[str, Dict[str, list]] = {
     "plx_conv": {
         "plx_gemm_nt": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P],
         "plx_gemm_nt_bndx": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P],
+        "plx_gemm_nt_bnapply": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P],
         "plx_gemm_nt_rows_per_block": [_I],
         "plx_gemm_tn_workspace": [_I, _I, _I, _I],
         "plx_set_tn_v2": [_I, _I],

@@ -14,7 +14,7 @@ from typing import Optional
 import torch
 
 from polyaxon_amd.ops import _native
-from polyaxon_amd.ops.conv1x1 import BnLink
+from polyaxon_amd.ops.conv1x1 import BnLink, PendingApply, fill_pending
 from polyaxon_amd.ops.flat import direct_grad
 
 
@@ -48,7 +48,7 @@ def supported(x: torch.Tensor) -> bool:
 class _BNAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var, residual, momentum, eps, relu, ext=None, box=None,
-                link=None, rlink=None, defer=False, dxsink=None):
+                link=None, rlink=None, defer=False, dxsink=None, pend=None):
         lib = _native.lib("plx_bn")
         # dxsink (ops.conv1x1.DxSink): x is a 1x1 convolution's output as is, and that convolution's data-gradient
         # GEMM can produce this BatchNorm's dx (the backward decides)
@@ -64,7 +64,10 @@ class _BNAct(torch.autograd.Function):
         # BatchNorm) applies scale/bias on the fly (link.affine); the backward is unchanged
         defer = bool(defer) and not relu and residual is None and link is not None
         y = None if defer else torch.empty_like(x, memory_format=torch.channels_last)
-        yp = y.data_ptr() if y is not None else None
+        # pend: reduce / finalize only -- y and the mask are allocated but left unwritten, and the forward GEMM of the
+        # 1x1 convolution that reads y fills them (ops.conv1x1.PendingApply, handed to bn_act through the list `pend`)
+        holder, pend = pend, pend is not None and relu and residual is not None and not defer
+        yp = y.data_ptr() if (y is not None and not pend) else None
         stats = torch.empty(4 * c, **f32)  # mean | invstd | scale | bias
         res_sb = None
         if residual is not None:
@@ -96,6 +99,9 @@ class _BNAct(torch.autograd.Function):
                 rsp, _counters(x.device), _stream())
             _native.check(rc, "plx_bn_forward")
         ctx.save_for_backward(x, mask, weight, stats)
+        ctx.pending = PendingApply(x, res, stats[2 * c:], res_sb, mask, y) if pend else None
+        if pend:
+            holder.append(ctx.pending)
         ctx.relu = relu
         ctx.has_res = residual is not None
         ctx.box = box if (box is not None and box.armed and residual is not None) else None
@@ -123,6 +129,8 @@ class _BNAct(torch.autograd.Function):
     def backward(ctx, dy):
         lib = _native.lib("plx_bn")
         x, mask, weight, stats = ctx.saved_tensors
+        if ctx.pending is not None:  # the mask read below was left to the consumer's GEMM (or materialize) to write
+            ctx.pending.check_done()
         n, c, h, w = x.shape
         m = n * h * w
         dy = _cl(dy)
@@ -164,7 +172,7 @@ class _BNAct(torch.autograd.Function):
                 ctx.box.put_masked(dy, mask)
             dgamma = dgb[:c] if dgb is not None else None
             dbeta = dgb[c:] if dgb is not None else None
-            return dx, dgamma, dbeta, None, None, None, None, None, None, None, None, None, None, None, None
+            return dx, dgamma, dbeta, None, None, None, None, None, None, None, None, None, None, None, None, None
         rb = None
         if ctx.rlink is not None and dres is not None:
             rl = ctx.rlink
@@ -198,7 +206,7 @@ class _BNAct(torch.autograd.Function):
             dres = None
         dgamma = dgb[:c] if dgb is not None else None
         dbeta = dgb[c:] if dgb is not None else None
-        return dx, dgamma, dbeta, None, None, dres, None, None, None, None, None, None, None, None, None
+        return dx, dgamma, dbeta, None, None, dres, None, None, None, None, None, None, None, None, None, None
 
 
 class _Materialize(torch.autograd.Function):
@@ -217,8 +225,13 @@ class _Materialize(torch.autograd.Function):
 
 
 def materialize(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
-    """The real value of a possibly deferred BatchNorm output (:func:`bn_act` with ``defer_apply``)."""
-    if t is None or not getattr(t, "_plx_deferred", False):
+    """The real value of a possibly deferred BatchNorm output: :func:`bn_act` with ``defer_apply`` (the raw input
+    plus its pending scale/bias), or with ``defer_res_relu`` (an unwritten output that no convolution took: the
+    standalone apply + residual + ReLU kernel fills it in place, :class:`~polyaxon_amd.ops.conv1x1.PendingApply`)."""
+    if t is None:
+        return t
+    fill_pending(t)
+    if not getattr(t, "_plx_deferred", False):
         return t
     return _Materialize.apply(t, t._plx_bn_link.affine)
 
@@ -226,7 +239,8 @@ def materialize(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
 def bn_act(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, running_mean: Optional[torch.Tensor],
            running_var: Optional[torch.Tensor], training: bool, momentum: float, eps: float,
            residual: Optional[torch.Tensor], act: bool, ext_stats=None, residual_grad_box=None,
-           residual_link: bool = False, defer_apply: bool = False, dx_sink=None) -> torch.Tensor:
+           residual_link: bool = False, defer_apply: bool = False, dx_sink=None,
+           defer_res_relu: bool = False) -> torch.Tensor:
     """``ext_stats`` = (fp32 [2][nblk][C] channel sums / sums of squares of ``x``, nblk) from the op that
     produced ``x`` (the 1x1-conv GEMM epilogue); training mode then skips the stats pass.  ``residual_link``:
     ``residual`` is the output of a fused BatchNorm that nothing else consumes; its backward partials are then
@@ -235,18 +249,26 @@ def bn_act(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, running_me
     the scale/bias while adding (a ResNet downsampling branch: ~0.3 ms of a bs-256 step), any other consumer
     must call :func:`materialize` first.  ``dx_sink``: the :class:`~polyaxon_amd.ops.conv1x1.DxSink` the 1x1
     convolution that produced ``x`` attached to it; the backward then leaves its dx pass to that convolution's
-    data-gradient GEMM whenever it has no d_residual tensor to write."""
+    data-gradient GEMM whenever it has no d_residual tensor to write.  ``defer_res_relu`` (training, activation and
+    residual): run the reduce / finalize only and return the *unwritten* output carrying ``_plx_pending`` (a
+    :class:`~polyaxon_amd.ops.conv1x1.PendingApply`); the caller guarantees that the next reader is a native 1x1
+    convolution, whose forward GEMM fills the output and the ReLU mask on the way (any other must call
+    :func:`materialize` first)."""
+    fill_pending(residual)  # a block output still pending (its convolution did not run first) is read below
     if residual is not None and residual.dtype != x.dtype:
         residual = residual.to(x.dtype)
     if training:
         link = BnLink()
         rlink = getattr(residual, "_plx_bn_link", None) if (residual_link and residual is not None) else None
         defer = bool(defer_apply) and not act and residual is None
+        pend = [] if (defer_res_relu and act and residual is not None) else None
         y = _BNAct.apply(x, weight, bias, running_mean, running_var, residual, momentum, eps, act, ext_stats,
-                         residual_grad_box, link, rlink, defer, dx_sink)
+                         residual_grad_box, link, rlink, defer, dx_sink, pend)
         y._plx_bn_link = link
         if defer:
             y._plx_deferred = True
+        if pend:
+            y._plx_pending = pend[0]
         return y
     residual = materialize(residual)
     # inference: fold running stats into scale/bias, one apply pass

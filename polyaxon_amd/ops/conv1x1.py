@@ -40,6 +40,22 @@ def set_bn_dx_fused(on: bool) -> bool:
     return prev
 
 
+# A/B knob, read once at load: 1 = a bottleneck's last BatchNorm leaves its apply + residual + ReLU pass to the forward
+# GEMM of the next block's conv1 (PendingApply, plx_gemm_nt_bnapply); 0 = the apply pass and the GEMM as two kernels
+_BN_APPLY_FUSED = os.environ.get("PLX_BN_APPLY_FUSED", "1") != "0"
+
+
+def set_bn_apply_fused(on: bool) -> bool:
+    """Switch the fused BatchNorm-apply forward GEMM for the forwards run from now on; returns the previous setting."""
+    global _BN_APPLY_FUSED
+    prev, _BN_APPLY_FUSED = _BN_APPLY_FUSED, bool(on)
+    return prev
+
+
+def bn_apply_fused() -> bool:
+    return _BN_APPLY_FUSED
+
+
 def _zero_page(dev: torch.device) -> torch.Tensor:
     idx = dev.index if dev.index is not None else torch.cuda.current_device()
     return _native.cached(_ZERO, idx, lambda: torch.zeros(256, dtype=torch.bfloat16, device=dev))
@@ -124,6 +140,39 @@ def gemm_nt_bndx(g: torch.Tensor, x: torch.Tensor, mask: torch.Tensor, coef: tor
                                                   add_mask.data_ptr() if add_mask is not None else None,
                                                   ctypes.addressof(bnr) if bnr is not None else None, _stream())
     _native.check(rc, "plx_gemm_nt_bndx")
+    return out
+
+
+def gemm_nt_bnapply(x: torch.Tensor, res: torch.Tensor, sb: torch.Tensor, rsb, out_a: torch.Tensor, mask: torch.Tensor,
+                    b: torch.Tensor, out: torch.Tensor = None, stats: torch.Tensor = None) -> torch.Tensor:
+    """The forward ``out[M][N] = out_a · bᵀ`` of a 1x1 convolution whose input ``out_a[M][K]`` is the output of the
+    bottleneck before it, produced by the GEMM itself: ``out_a = relu(x·sb[0] + sb[1] + (res·rsb[0] + rsb[1]))`` per
+    channel (``res`` as is without ``rsb``), rounded to bf16 once, written to ``out_a`` with its sign bits to ``mask``
+    (both bit-identical to the standalone apply pass) and consumed as the GEMM's A operand.  ``x``, ``res``,
+    ``out_a``: dense bf16 rows; ``mask``: uint8 [M·K/8]; ``sb``, ``rsb`` (or None): fp32 [2·K]; ``stats`` as
+    :func:`gemm_nt`."""
+    m, k = x.shape
+    n = b.shape[0]
+    if out is None:
+        out = torch.empty(m, n, dtype=torch.bfloat16, device=x.device)
+    for t in (x, res, out_a):
+        assert t.shape == (m, k) and t.dtype == torch.bfloat16 and t.stride() == (k, 1) and t.data_ptr() % 16 == 0
+    assert b.stride(1) == 1 and out.stride(1) == 1 and b.shape[1] == k and b.dtype == torch.bfloat16
+    assert b.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0
+    assert mask.dtype == torch.uint8 and mask.is_contiguous() and mask.numel() >= m * k // 8
+    for c in (sb, rsb):
+        assert c is None or (c.dtype == torch.float32 and c.is_contiguous() and c.numel() == 2 * k
+                             and c.data_ptr() % 16 == 0)
+    assert sb is not None
+    if stats is not None:
+        nblk = -(-m // nt_stats_rows(n))
+        assert stats.dtype == torch.float32 and stats.is_contiguous() and stats.numel() >= 2 * nblk * n
+    rc = _native.lib("plx_conv").plx_gemm_nt_bnapply(x.data_ptr(), res.data_ptr(), sb.data_ptr(),
+                                                     rsb.data_ptr() if rsb is not None else None, out_a.data_ptr(),
+                                                     mask.data_ptr(), b.data_ptr(), out.data_ptr(), m, n, k,
+                                                     b.stride(0), out.stride(0),
+                                                     stats.data_ptr() if stats is not None else None, _stream())
+    _native.check(rc, "plx_gemm_nt_bnapply")
     return out
 
 
@@ -251,6 +300,71 @@ def dx_sink_for(x: torch.Tensor, weight: torch.Tensor):
     return DxSink() if (cout >= 2 * cin and cin <= 128) else None
 
 
+class PendingApply:
+    """A bottleneck's last BatchNorm → the 1x1 convolution that reads the block output, for the forward: the
+    BatchNorm leaves its apply + residual + ReLU pass to the convolution's forward GEMM (:func:`gemm_nt_bnapply`).
+
+    The BatchNorm (``ops.bn_fused.bn_act(defer_res_relu=True)``) runs its reduce / finalize only and returns the
+    *unwritten* output carrying one of these (``out._plx_pending``) with what the apply pass would have read: the raw
+    input ``x``, the residual ``res``, ``sb`` (fp32 [scale | bias]), ``rsb`` (the residual's deferred affine or None)
+    and the ``mask`` buffer.  The model only asks for this when the next op is a supported native 1x1 convolution
+    (``models.resnet``), which ``take``s the payload and whose GEMM fills ``out`` and ``mask`` on the way; any other
+    consumer goes through :meth:`fill` (``ops.bn_fused.materialize``), the standalone apply kernel.  Nothing may read
+    ``out`` or ``mask`` before either happened: a second ``take`` raises, and so does the BatchNorm's backward when
+    the payload is still pending (:meth:`check_done`).  The payload keeps the operands alive."""
+
+    __slots__ = ("x", "res", "sb", "rsb", "mask", "out", "state")
+
+    def __init__(self, x, res, sb, rsb, mask, out):
+        self.x, self.res, self.sb, self.rsb, self.mask, self.out = x, res, sb, rsb, mask, out
+        self.state = "pending"  # -> "taken" (a GEMM fills it) or "filled" (the standalone pass did)
+
+    @property
+    def pending(self) -> bool:
+        return self.state == "pending"
+
+    def take(self) -> "PendingApply":
+        if self.state != "pending":
+            raise RuntimeError("PendingApply: the deferred BatchNorm output was already " + self.state
+                               + "; a second consumer cannot take it")
+        self.state = "taken"
+        return self
+
+    def fill(self) -> None:
+        """The standalone apply + residual + ReLU pass into ``out`` and ``mask`` (no-op once done)."""
+        if self.state != "pending":
+            return
+        n, c, h, w = self.x.shape
+        rc = _native.lib("plx_bn").plx_bn_apply_res_relu(
+            self.x.data_ptr(), self.res.data_ptr(), self.out.data_ptr(), n * h * w, c, self.sb.data_ptr(),
+            self.mask.data_ptr(), self.rsb.data_ptr() if self.rsb is not None else None, _stream())
+        _native.check(rc, "plx_bn_apply_res_relu")
+        self.state = "filled"
+        self.release()
+
+    def release(self) -> None:  # the operands, and the references that make a cycle with the output tensor
+        self.x = self.res = self.sb = self.rsb = self.mask = self.out = None
+
+    def check_done(self) -> None:
+        if self.state == "pending":
+            raise RuntimeError("PendingApply: the BatchNorm's deferred output (and its ReLU mask) was never filled: "
+                               "no consumer took it and nothing materialised it before the backward")
+
+
+def fill_pending(t):
+    """``t`` with a still pending deferred apply (:class:`PendingApply`) filled by the standalone kernel."""
+    p = getattr(t, "_plx_pending", None) if t is not None else None
+    if p is not None:
+        p.fill()
+    return t
+
+
+def bn_apply_sink_ok(cin: int, cout: int) -> bool:
+    """The shape-class rule of the fused BatchNorm-apply forward GEMM, :func:`dx_sink_for`'s mirrored: the GEMM's K
+    (= Cin) is at least twice its N (= Cout), and N fits one tile (N <= 128)."""
+    return _BN_APPLY_FUSED and cin >= 2 * cout and cout <= 128
+
+
 class BnLink:
     """A fused BatchNorm(+ReLU)'s output → the convolution whose data gradient is that output's COMPLETE gradient.
 
@@ -321,7 +435,11 @@ def bn_link_of(x: torch.Tensor, want: bool):
 
 class _Conv1x1(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, stats, box, sink, link, dxsink=None):
+    def forward(ctx, x, weight, stats, box, sink, link, dxsink=None, pend=None):
+        if pend is not None and (x.data_ptr() != pend.out.data_ptr() or x.shape != pend.out.shape
+                                 or x.dtype != torch.bfloat16
+                                 or not x.is_contiguous(memory_format=torch.channels_last)):
+            raise RuntimeError("PendingApply: the convolution's input is not the deferred BatchNorm output")
         x = x.to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
         ctx.box = box
         ctx.dxsink = dxsink
@@ -336,7 +454,11 @@ class _Conv1x1(torch.autograd.Function):
         cout = weight.shape[0]
         wb, wt = wcache.lookup(weight) or weight_prep(weight)
         y = torch.empty((n, cout, h, w), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
-        gemm_nt(_rows(x), wb, _rows(y), stats)
+        if pend is not None:  # fills x (the block output before this conv) and its mask, and reads x as the A operand
+            gemm_nt_bnapply(_rows(pend.x), _rows(pend.res), pend.sb, pend.rsb, _rows(x), pend.mask, wb, _rows(y), stats)
+            pend.release()
+        else:
+            gemm_nt(_rows(x), wb, _rows(y), stats)
         ctx.save_for_backward(x, wt)
         ctx.wshape = weight.shape
         ctx.wdtype = weight.dtype
@@ -390,7 +512,7 @@ class _Conv1x1(torch.autograd.Function):
                 side_stream.run(lambda: gemm_tn(_rows(dy), _rows(x), out=slot, accumulate=True), (dy, x), x.device)
             else:
                 dw = gemm_tn(_rows(dy), _rows(x)).view(ctx.wshape).to(ctx.wdtype)
-        return dx, dw, None, None, None, None, None
+        return dx, dw, None, None, None, None, None, None
 
 
 def _bf16_context(x: torch.Tensor) -> bool:
@@ -422,7 +544,19 @@ def conv1x1(x: torch.Tensor, weight: torch.Tensor, with_stats: bool = False,
     if grad_box is not None:
         grad_box.armed = True
     dxsink = dx_sink_for(x, weight)
-    y = _Conv1x1.apply(x, weight, stats, grad_box, grad_sink, bn_link_of(x, bn_link), dxsink)
+    # the block output whose apply + residual + ReLU was left to this conv (PendingApply): taken when the shape class is
+    # the fused GEMM's, else filled by the standalone pass
+    pend = getattr(x, "_plx_pending", None)
+    if pend is not None and pend.pending:
+        n, cin, h, w = x.shape
+        if bn_apply_sink_ok(cin, weight.shape[0]) and n * h * w * cin < (1 << 30):
+            pend = pend.take()
+        else:
+            pend.fill()
+            pend = None
+    else:
+        pend = None
+    y = _Conv1x1.apply(x, weight, stats, grad_box, grad_sink, bn_link_of(x, bn_link), dxsink, pend)
     if stats is not None:
         y._plx_channel_stats = (stats, nblk)
     if dxsink is not None:
@@ -444,4 +578,4 @@ class Conv1x1(nn.Conv2d):
         if self.native and supported(x, self):
             return conv1x1(x, self.weight, with_stats=self.bn_stats and self.training, grad_box=grad_box,
                            grad_sink=grad_sink, bn_link=bn_link)
-        return F.conv2d(x, self.weight, None, self.stride)
+        return F.conv2d(fill_pending(x), self.weight, None, self.stride)

@@ -50,9 +50,10 @@ class BatchNormAct(nn.Module):
             self.running_var.fill_(1.0)
 
     def forward(self, x: torch.Tensor, identity: Optional[torch.Tensor] = None, residual_grad_box=None,
-                residual_link: bool = False, defer_apply: bool = False) -> torch.Tensor:
+                residual_link: bool = False, defer_apply: bool = False, defer_res_relu: bool = False) -> torch.Tensor:
         """``defer_apply``: the caller guarantees the output feeds only the residual add of another
-        BatchNormAct (see ``ops.bn_fused.bn_act``)."""
+        BatchNormAct (see ``ops.bn_fused.bn_act``).  ``defer_res_relu``: the caller guarantees the output's next
+        reader is a native 1x1 convolution that fills it (ibid.; ignored off the fused path)."""
         if self.residual and identity is None:
             raise ValueError("BatchNormAct(residual=True) needs the identity tensor")
         if self.fused and x.is_cuda:
@@ -62,7 +63,8 @@ class BatchNormAct(nn.Module):
                 return bn_fused.bn_act(x, self.weight, self.bias, self.running_mean, self.running_var,
                                        self.training, self.momentum, self.eps, identity, self.act, ext,
                                        residual_grad_box, residual_link, defer_apply,
-                                       getattr(x, "_plx_dx_sink", None))  # set by ops.conv1x1 on its output
+                                       getattr(x, "_plx_dx_sink", None),  # set by ops.conv1x1 on its output
+                                       defer_res_relu)
         if identity is not None and identity.is_cuda:
             from polyaxon_amd.ops.bn_fused import materialize
             identity = materialize(identity)
