@@ -22,6 +22,10 @@
 //                     plx_adamw_mixed_clip read that state: they scale the gradient, or, on a non-finite norm, only
 //                     zero it.  Squares accumulate in fp32, so a gradient norm beyond about 1.8e19 (the square root
 //                     of FLT_MAX) overflows a partial and counts as non-finite: the step is skipped.
+//   plx_lr_schedule   learning-rate schedule as device data: one wave turns an 8-float schedule descriptor (base LR,
+//                     kind, warm-up, horizon, floor, decay) and the device step counter into hp[0] ahead of the step's
+//                     optimizer launches, so one captured step serves every schedule and a restored step counter
+//                     continues its curve.
 //
 // All memory-bound kernels use 16-byte (float4) accesses and a grid capped at 2048 blocks with a
 // grid-stride loop (cdna_hip_programming.md Guideline 11/13).
@@ -597,6 +601,56 @@ __global__ void commit_metric_kernel(const float* __restrict__ ring, const int* 
   }
 }
 
+// ---------------------------------------------------------------- learning-rate schedule
+// hp[0] = base_lr * f(s), s = *step = completed steps (the optimizers' t is s + 1); one wave, lane 0, fp32.
+// sched layout (fp32, device): [0] base_lr, [1] kind (0 constant, 1 linear, 2 cosine, 3 step, 4 inv_sqrt),
+// [2] warmup_steps W, [3] lr_total_steps T, [4] min_lr_ratio m, [5] lr_decay_gamma, [6] lr_decay_every E, [7] 0.
+// Steps are floats holding integers (exact below 2^24; the host rejects larger ones).
+//   s < W:     f = (s + 1) / W
+//   otherwise  p = clamp((s - W) / max(1, T - W), 0, 1) and
+//     constant f = 1                                  linear   f = 1 - (1 - m) p
+//     cosine   f = m + (1 - m) (1 + cos(pi p)) / 2    step     f = max(m, gamma^((s - W) div max(1, E)))
+//     inv_sqrt f = max(m, sqrt(max(W, 1) / (s + 1)))
+//   linear / cosine: T <= W (no horizon) holds f = 1; p = 1 (s >= T) is exactly m.
+// Wherever f is 1 it is the constant 1.0f, never the result of the arithmetic, so hp[0] is then bitwise base_lr.
+__device__ float lr_factor(const float* __restrict__ sched, int s) {
+  const int kind = (int)sched[1];
+  const float W = sched[2], T = sched[3], m = sched[4];
+  const float sf = (float)s;
+  if (sf < W) return sf + 1.f == W ? 1.f : (sf + 1.f) / W;
+  if (kind == 1 || kind == 2) {
+    if (T <= W || m == 1.f) return 1.f;
+    const float span = T - W;  // >= 1: both hold integers
+    float p = (sf - W) / span;
+    if (p <= 0.f) return 1.f;
+    if (p >= 1.f) return m;
+    if (kind == 1) return 1.f - (1.f - m) * p;
+    return m + (1.f - m) * 0.5f * (1.f + cosf(3.14159265358979323846f * p));
+  }
+  if (kind == 3) {
+    const int every = sched[6] >= 1.f ? (int)sched[6] : 1;
+    const int k = (s - (int)W) / every;
+    if (k == 0) return 1.f;
+    const float d = powf(sched[5], (float)k);
+    return d > m ? d : m;
+  }
+  if (kind == 4) {
+    const float w = W > 1.f ? W : 1.f;
+    if (sf + 1.f == w) return 1.f;
+    const float d = sqrtf(w / (sf + 1.f));
+    return d > m ? d : m;
+  }
+  return 1.f;
+}
+
+__global__ __launch_bounds__(64) void lr_schedule_kernel(const float* __restrict__ sched,
+                                                         const int* __restrict__ step, float* __restrict__ hp) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    const float f = lr_factor(sched, *step);
+    hp[0] = f == 1.f ? sched[0] : sched[0] * f;
+  }
+}
+
 }  // namespace
 
 // The optimizer launches, shared by the plain entry points (state == nullptr: the kernels without clipping) and the
@@ -771,5 +825,13 @@ PLX_API int plx_record_metric(const void* loss, int is_bf16, float* ring, int* s
 PLX_API int plx_commit_metric(const float* ring, const int* step, int ring_size, int window, float* out, int slot,
                               hipStream_t stream) {
   hipLaunchKernelGGL(commit_metric_kernel, dim3(1), dim3(256), 0, stream, ring, step, ring_size, window, out, slot);
+  return (int)hipGetLastError();
+}
+
+// hp[0] = sched[0] * f(*step) (lr_schedule_kernel): queued ahead of the step's optimizer launch(es) on their stream,
+// ordered by the launch boundary alone.  It writes hp[0] and nothing else.
+PLX_API int plx_lr_schedule(const float* sched, const int* step, float* hp, hipStream_t stream) {
+  if (sched == nullptr || step == nullptr || hp == nullptr) return 1;
+  hipLaunchKernelGGL(lr_schedule_kernel, dim3(1), dim3(64), 0, stream, sched, step, hp);
   return (int)hipGetLastError();
 }

@@ -215,6 +215,7 @@ SIGNATURES: Dict[str, Dict[str, list]] = {
         "plx_gradnorm_blocks": [_L],
         "plx_gradnorm_partials": [_P, _I, _L, _P, _P],
         "plx_gradnorm_finalize": [_P, _I, _P, _P, _P],
+        "plx_lr_schedule": [_P, _P, _P, _P],
         "plx_cast_lp": [_P, _P, _L, _P],
         "plx_init_flat": [_P, _P, _P, _P, _I, _P, _P, _U64, _P],
         "plx_zero_flat": [_P, _L, _P],

@@ -11,15 +11,21 @@ that tensor, and the norm, the scale and the skip of a non-finite step are compu
 (``plx_gradnorm_partials`` / ``plx_gradnorm_finalize`` / the ``*_clip`` optimizer kernels), so a captured step
 clips every trial to its own threshold without a host sync or a re-capture.
 
+Learning-rate schedules (``lr_schedule=``, opt-in) are device data too: an 8-float ``sched`` tensor (base LR, kind,
+warm-up, horizon, floor, decay) that ``plx_lr_schedule`` turns into ``hp[0]`` from the device step counter, one tiny
+launch ahead of the step's optimizer launches.  A trial changes its schedule -- kind included -- with one more
+32-byte copy; snapshots restore the step counter, so a resumed trial continues its curve with nothing else saved.
+
 On CPU (no native library) the same update is computed with torch ops; tests compare the two.
 """
 from __future__ import annotations
 
+import math
 from typing import Dict, Optional
 
 import torch
 
-from polyaxon_amd.ops import _native, side_stream
+from polyaxon_amd.ops import _native, lr_schedule as _lrs, side_stream
 from polyaxon_amd.ops.flat import FlatParams
 
 
@@ -52,14 +58,16 @@ class _PinnedRing:
         self.events[i] = ev
 
 
-def _set_hp(opt, values) -> None:
-    if not opt.hp.is_cuda:
-        opt.hp.copy_(torch.tensor(values, dtype=torch.float32))
+def _set_hp(opt, values, dst: Optional[torch.Tensor] = None) -> None:
+    """``dst`` (default ``opt.hp``; the 8-float ``sched`` tensor of a scheduled optimizer) := ``values``."""
+    dst = opt.hp if dst is None else dst
+    if not dst.is_cuda:
+        dst.copy_(torch.tensor(values, dtype=torch.float32))
         return
     ring = getattr(opt, "_ring", None)
     if ring is None:
         ring = opt._ring = _PinnedRing(width=opt.hp.numel())
-    ring.copy_to(opt.hp, values)
+    ring.copy_to(dst, values)
 
 
 class _GradClip:
@@ -162,16 +170,126 @@ class _Clipping:
         return self._need_clip().stats()
 
 
-class FusedSGD(_Clipping):
+def lr_factor(kind, s, W, T, m, gamma, E) -> torch.Tensor:
+    """The factor ``plx_lr_schedule`` multiplies the base LR by at ``s`` completed steps, in torch float32 (the CPU
+    path, and the twin the tests hold the kernel against).  ``kind``: a name or code of ops/lr_schedule.py KINDS;
+    W warm-up steps, T horizon (``lr_total_steps``), m ``min_lr_ratio``, gamma / E the ``step`` kind's decay.
+
+    ``s < W``: (s + 1) / W.  After it, with p = clamp((s - W) / max(1, T - W), 0, 1): constant 1; linear
+    1 - (1 - m) p; cosine m + (1 - m) (1 + cos(pi p)) / 2; step max(m, gamma^((s - W) // max(1, E))); inv_sqrt
+    max(m, sqrt(max(W, 1) / (s + 1))).  Linear and cosine hold 1 when T <= W (no horizon) and are exactly m from
+    s = T on.  Wherever the factor is 1 it is exactly 1.0, so ``base_lr * factor`` is then bitwise ``base_lr``."""
+    def f32(x):
+        return torch.tensor(float(x), dtype=torch.float32)
+
+    code = _lrs.kind_code(kind)
+    s, W, E = int(s), int(W), int(E)
+    one, sf, Wf, Tf, m, gamma = f32(1.0), f32(s), f32(W), f32(T), f32(m), f32(gamma)
+    if s < W:
+        return one if s + 1 == W else (sf + 1.0) / Wf
+    if code in (1, 2):
+        if float(Tf) <= W or float(m) == 1.0:
+            return one
+        p = (sf - Wf) / (Tf - Wf)
+        if float(p) <= 0.0:
+            return one
+        if float(p) >= 1.0:
+            return m
+        if code == 1:
+            return 1.0 - (1.0 - m) * p
+        return m + (1.0 - m) * 0.5 * (1.0 + torch.cos(f32(math.pi) * p))
+    if code == 3:
+        k = (s - W) // max(1, E)
+        return one if k == 0 else torch.maximum(m, torch.pow(gamma, f32(k)))
+    if code == 4:
+        w = f32(max(W, 1))
+        return one if s + 1 == max(W, 1) else torch.maximum(m, torch.sqrt(w / (sf + 1.0)))
+    return one
+
+
+class _LrSchedule:
+    """The device side of ``lr_schedule=``: the 8-float ``sched`` tensor -- [0] base LR, [1] kind code, [2]
+    ``warmup_steps``, [3] ``lr_total_steps``, [4] ``min_lr_ratio``, [5] ``lr_decay_gamma``, [6] ``lr_decay_every``,
+    [7] 0 -- and the launch that evaluates it into ``hp[0]``.  Allocated here, never during a capture."""
+
+    def __init__(self, flat: FlatParams):
+        self.sched = torch.zeros(8, dtype=torch.float32, device=flat.device)
+        self.queued = False  # per-bucket updates: this step's evaluation is already on the optimizer stream
+
+    def values(self, host: Dict[str, float]):
+        return [host["lr"]] + [host[k] for k in _lrs.KEYS] + [0.0]
+
+    def evaluate(self, hp: torch.Tensor, step: torch.Tensor, stream: Optional[int]) -> None:
+        """hp[0] = base LR x factor(step): one ``plx_lr_schedule`` launch on ``stream`` (GPU), torch float32 on CPU."""
+        if not hp.is_cuda:
+            v = self.sched.tolist()
+            hp[0] = self.sched[0] * lr_factor(int(v[1]), int(step.item()), *v[2:7])
+            return
+        st = stream if stream is not None else _stream_ptr(hp)
+        _native.check(_native.lib("plx_train").plx_lr_schedule(self.sched.data_ptr(), step.data_ptr(), hp.data_ptr(),
+                                                               st), "plx_lr_schedule")
+
+
+class _Scheduled:
+    """The ``lr_schedule`` surface the fused optimizers share.  ``lr_schedule=None`` (default): no schedule -- the
+    hyper-parameters do not exist, nothing is allocated, the launches are the ones without it.  With a kind name
+    this instance's ``HP`` gains ops/lr_schedule.py KEYS, ``lr`` becomes the base LR, and every step evaluates the
+    schedule on the device before its update; ``set_hparams(lr_schedule=<name or code>, ...)`` changes all of it,
+    the kind included, per trial."""
+
+    _sched: Optional[_LrSchedule] = None
+
+    def _init_sched(self, flat: FlatParams, lr_schedule: Optional[str]) -> Dict[str, float]:
+        """Returns the schedule hyper-parameters the constructor's first ``set_hparams`` sets (none when off)."""
+        if lr_schedule is None:
+            return {}
+        code = _lrs.kind_code(lr_schedule)
+        self.HP = self.HP + _lrs.KEYS  # this instance only; they live in ``sched``, not in ``hp``
+        self._sched = _LrSchedule(flat)
+        return dict(_lrs.DEFAULTS, lr_schedule=code)
+
+    @property
+    def scheduled(self) -> bool:
+        return self._sched is not None
+
+    def _set_hparams(self, what: str, hp) -> None:
+        """Validate, merge into the host copy and upload: ``hp`` (every key that is no schedule key, in ``HP``
+        order) and, for a scheduled optimizer, ``sched`` -- both through the pinned ring."""
+        vals = getattr(self, "_hp_host", None) or {k: 0.0 for k in self.HP}
+        new = {}
+        for k, v in hp.items():
+            if k not in self.HP:
+                raise KeyError(f"unknown {what} hyper-parameter {k!r}")
+            new[k] = _lrs.validate(k, v) if k in _lrs.KEYS else float(v)
+        vals.update(new)  # only once every value has passed
+        self._hp_host = vals
+        keys = [k for k in self.HP if k not in _lrs.KEYS] if self._sched is not None else self.HP
+        _set_hp(self, [vals[k] for k in keys] + [0.0] * (8 - len(keys)))
+        if self._sched is not None:
+            _set_hp(self, self._sched.values(vals), self._sched.sched)
+
+    def _schedule_lr(self, stream: Optional[int] = None) -> None:
+        if self._sched is not None:
+            self._sched.evaluate(self.hp, self.step, stream)
+
+    def current_lr(self) -> torch.Tensor:
+        """The learning rate of the last step (scheduled: base LR x factor at that step; before the first step, and
+        without a schedule, ``lr`` itself): the 0-dim view ``hp[0]`` of the device hyper-parameters (no sync)."""
+        return self.hp[0]
+
+
+class FusedSGD(_Clipping, _Scheduled):
     """SGD with momentum / nesterov / dampening and weight decay on the decay segment only."""
 
     HP = ("lr", "momentum", "weight_decay", "nesterov", "dampening")
 
     def __init__(self, flat: FlatParams, lr: float = 0.1, momentum: float = 0.9, weight_decay: float = 1e-4,
                  nesterov: bool = False, dampening: float = 0.0, step_counter: Optional[torch.Tensor] = None,
-                 max_grad_norm: Optional[float] = None):
+                 max_grad_norm: Optional[float] = None, lr_schedule: Optional[str] = None):
         """``max_grad_norm``: a number enables global-norm gradient clipping for the optimizer's lifetime (a device
-        hyper-parameter like the others; 0 = measure the norm, no limit); None: no clipping at all."""
+        hyper-parameter like the others; 0 = measure the norm, no limit); None: no clipping at all.
+        ``lr_schedule``: a kind name (ops/lr_schedule.py KINDS) enables the device-resident LR schedule for the
+        optimizer's lifetime, ``lr`` being its base LR; None: constant ``lr``, no schedule at all."""
         self.flat = flat
         dev = flat.device
         self.momentum_buf = torch.zeros_like(flat.params)
@@ -179,17 +297,12 @@ class FusedSGD(_Clipping):
         # step counter shared with the metric ring: 0 right after reset() => momentum := grad
         self.step = step_counter if step_counter is not None else torch.zeros(1, dtype=torch.int32, device=dev)
         self._init_clip(flat, max_grad_norm)
+        sched = self._init_sched(flat, lr_schedule)
         self.set_hparams(lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=nesterov,
-                         dampening=dampening, **({"max_grad_norm": max_grad_norm} if self.clipping else {}))
+                         dampening=dampening, **({"max_grad_norm": max_grad_norm} if self.clipping else {}), **sched)
 
     def set_hparams(self, **hp) -> None:
-        vals = getattr(self, "_hp_host", {k: 0.0 for k in self.HP})
-        for k, v in hp.items():
-            if k not in self.HP:
-                raise KeyError(f"unknown SGD hyper-parameter {k!r}")
-            vals[k] = float(v)
-        self._hp_host = vals
-        _set_hp(self, [vals[k] for k in self.HP] + [0.0] * (8 - len(self.HP)))
+        self._set_hparams("SGD", hp)
 
     def reset_state(self) -> None:
         if self.flat.params.is_cuda:
@@ -205,6 +318,7 @@ class FusedSGD(_Clipping):
         f.grads_consumed()
         if f.lp_params is not None:
             raise NotImplementedError("FusedSGD has no mixed-precision (lp) flat mode; use FusedAdamW")
+        self._schedule_lr()  # hp[0] of this step, ahead of the norm pass and the update
         if not f.params.is_cuda:
             self._step_reference()
         elif self._clip is not None:
@@ -244,16 +358,19 @@ class FusedSGD(_Clipping):
         return {"momentum": self.momentum_buf}
 
 
-class FusedAdamW(_Clipping):
+class FusedAdamW(_Clipping, _Scheduled):
     HP = ("lr", "beta1", "beta2", "eps", "weight_decay")
 
     def __init__(self, flat: FlatParams, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 1e-2, step_counter: Optional[torch.Tensor] = None,
-                 max_grad_norm: Optional[float] = None):
+                 max_grad_norm: Optional[float] = None, lr_schedule: Optional[str] = None):
         """``max_grad_norm``: a number enables global-norm gradient clipping for the optimizer's lifetime (a device
         hyper-parameter like the others; 0 = measure the norm, no limit); None: no clipping at all.  Clipping needs
         the whole gradient before any update, so it excludes the per-bucket updates (``step_range_``,
-        ``FlatDDP(optimizer=...)``)."""
+        ``FlatDDP(optimizer=...)``).
+        ``lr_schedule``: a kind name (ops/lr_schedule.py KINDS) enables the device-resident LR schedule for the
+        optimizer's lifetime, ``lr`` being its base LR; None: constant ``lr``, no schedule at all.  Per-bucket
+        updates are supported: the step's first ``step_range_`` evaluates the schedule on its stream."""
         self.flat = flat
         dev = flat.device
         self.exp_avg = torch.zeros_like(flat.params)
@@ -261,17 +378,12 @@ class FusedAdamW(_Clipping):
         self.hp = torch.zeros(8, dtype=torch.float32, device=dev)
         self.step = step_counter if step_counter is not None else torch.zeros(1, dtype=torch.int32, device=dev)
         self._init_clip(flat, max_grad_norm)
+        sched = self._init_sched(flat, lr_schedule)
         self.set_hparams(lr=lr, beta1=betas[0], beta2=betas[1], eps=eps, weight_decay=weight_decay,
-                         **({"max_grad_norm": max_grad_norm} if self.clipping else {}))
+                         **({"max_grad_norm": max_grad_norm} if self.clipping else {}), **sched)
 
     def set_hparams(self, **hp) -> None:
-        vals = getattr(self, "_hp_host", {k: 0.0 for k in self.HP})
-        for k, v in hp.items():
-            if k not in self.HP:
-                raise KeyError(f"unknown AdamW hyper-parameter {k!r}")
-            vals[k] = float(v)
-        self._hp_host = vals
-        _set_hp(self, [vals[k] for k in self.HP] + [0.0] * (8 - len(self.HP)))
+        self._set_hparams("AdamW", hp)
 
     def reset_state(self) -> None:
         self.exp_avg.zero_()
@@ -297,10 +409,13 @@ class FusedAdamW(_Clipping):
     def step_(self) -> None:
         f = self.flat
         f.grads_consumed()  # every kernel below zeroes the gradients it reads
+        if self._sched is not None:
+            self._sched.queued = False  # the next step's first step_range_ evaluates the schedule again
         if self.in_backward:
             return  # every bucket was already updated (FlatDDP.finish joined the optimizer stream)
         if self.sharded:
             raise RuntimeError("sharded AdamW state is updated per bucket by FlatDDP; step_() alone would skip it")
+        self._schedule_lr()  # hp[0] of this step, ahead of the norm pass and the update
         if not f.params.is_cuda:
             self._step_reference()
             return
@@ -359,6 +474,11 @@ class FusedAdamW(_Clipping):
                              "per-range step (step_range_, FlatDDP(optimizer=...), ZeRO-1)")
         f = self.flat
         so = lo if state_off is None else state_off
+        if self._sched is not None and not self._sched.queued:
+            # the step's first range: every range of a step runs on one stream (FlatDDP's optimizer stream), so the
+            # launch boundary orders hp[0] ahead of all of them; step_() re-arms the flag
+            self._schedule_lr(stream)
+            self._sched.queued = True
         if not f.params.is_cuda:
             self._step_reference_range(lo, hi, so)
             return

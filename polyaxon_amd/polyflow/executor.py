@@ -51,12 +51,16 @@ class ResidentTrialExecutor:
                  loss_fn: Optional[Callable] = None, optimizer: str = "sgd", use_graph: bool = True,
                  amp_dtype: Optional[torch.dtype] = torch.bfloat16, channels_last: bool = True,
                  ring_size: int = 4096, init_spec: Optional[Callable] = None,
-                 lp_dtype: Optional[torch.dtype] = None, clip_grad: bool = False):
+                 lp_dtype: Optional[torch.dtype] = None, clip_grad: bool = False, lr_schedule=False):
         """``lp_dtype`` (the language models, GPU): the model computes from bf16 weights with bf16 gradients and the
         optimizer keeps the fp32 master (ops/flat.py lp mode); every re-init / restore refreshes the bf16 copy.
         ``clip_grad``: global-norm gradient clipping (ops/optim.py) with ``max_grad_norm`` as one more device
         hyper-parameter: enabled with no limit (0) until a trial sets one, so the same captured step serves every
-        threshold."""
+        threshold.
+        ``lr_schedule`` (True or a kind name): the device-resident LR schedule (ops/optim.py) with its kind, warm-up,
+        horizon, floor and decay as more device hyper-parameters: True enables it as kind ``constant`` with no
+        warm-up -- bitwise the unscheduled step -- until a trial sets something else, so the same captured step
+        serves every schedule and every kind."""
         self.device = torch.device(device)
         self.is_cuda = self.device.type == "cuda"
         if channels_last:
@@ -68,10 +72,11 @@ class ResidentTrialExecutor:
         self._flatten_buffers()
         self.step = torch.zeros(1, dtype=torch.int32, device=self.device)
         clip = 0.0 if clip_grad else None
+        sched = ("constant" if lr_schedule is True else lr_schedule) or None
         if optimizer == "sgd":
-            self.opt = FusedSGD(self.flat, step_counter=self.step, max_grad_norm=clip)
+            self.opt = FusedSGD(self.flat, step_counter=self.step, max_grad_norm=clip, lr_schedule=sched)
         elif optimizer == "adamw":
-            self.opt = FusedAdamW(self.flat, step_counter=self.step, max_grad_norm=clip)
+            self.opt = FusedAdamW(self.flat, step_counter=self.step, max_grad_norm=clip, lr_schedule=sched)
         else:
             raise ValueError(f"unknown optimizer {optimizer!r}")
         # default: cross entropy of the fp32-cast logits; on the GPU in one fused HIP kernel each way (ops/lm.py
@@ -303,6 +308,11 @@ class ResidentTrialExecutor:
     def clip_stats(self) -> Dict[str, float]:
         """``clip_grad``: host floats {grad_norm, scale, skipped} of the last step; synchronises."""
         return self.opt.clip_stats()
+
+    def current_lr(self) -> torch.Tensor:
+        """The learning rate of the last step (``lr_schedule``: base LR x the schedule's factor at that step), a
+        0-dim device view (no sync)."""
+        return self.opt.current_lr()
 
     def run(self, n_steps: int) -> None:
         for _ in range(n_steps):

@@ -12,6 +12,12 @@ Registry: ``resnet50`` (BASELINE.json config 3), ``resnet_tiny`` (same code path
 
 Every built-in program takes ``params: {clip_grad: true}``: global-norm gradient clipping in the step, with
 ``max_grad_norm`` as one more per-trial hyper-parameter (device data like the rest; 0 = no limit).
+
+Every built-in program also takes ``params: {lr_schedule: true | <kind>}``: the device-resident LR schedule
+(ops/optim.py) with ``lr_schedule`` (constant, linear, cosine, step, inv_sqrt), ``warmup_steps``, ``lr_total_steps``,
+``min_lr_ratio``, ``lr_decay_gamma`` and ``lr_decay_every`` as per-trial hyper-parameters and ``lr`` as the base LR;
+``true`` starts every trial at ``constant``.  A trial that names no ``lr_total_steps`` gets the horizon from the
+sweep driver (``params: {lr_horizon: max | rung}``, default ``max``; ops/lr_schedule.py horizon_steps).
 """
 from __future__ import annotations
 
@@ -47,6 +53,10 @@ class TrialProgram:
             ex.snapshot("__warm__")
             ex.restore("__warm__")
             ex.drop("__warm__")
+            if self.info.get("lr_schedule"):  # back from the warm-up's schedule to the program's own kind
+                from polyaxon_amd.ops import lr_schedule as lrs
+
+                ex.set_hparams(**dict(lrs.DEFAULTS, lr_schedule=self.info["lr_schedule"]))
         if ex.is_cuda:
             torch.cuda.synchronize(ex.device)
 
@@ -62,6 +72,39 @@ def _with_clip(prog: TrialProgram, clip: bool) -> TrialProgram:
         prog.info["warm_hparams"] = {**prog.info.get("warm_hparams", {}), "max_grad_norm": 1.0}
         prog.info["clip_grad"] = True
     return prog
+
+
+def _lr_schedule(params: Dict[str, Any]):
+    """The program's ``lr_schedule`` param as the executor takes it: False, or a kind name (true = constant)."""
+    from polyaxon_amd.ops import lr_schedule as lrs
+
+    v = params.get("lr_schedule", False)
+    if v is None or v is False:
+        return False
+    return "constant" if v is True else lrs.KINDS[lrs.kind_code(v)]
+
+
+def _with_schedule(prog: TrialProgram, params: Dict[str, Any]) -> TrialProgram:
+    """``lr_schedule`` programs understand the schedule's keys, warm up on a cosine schedule with warm-up (so the
+    warm steps run the kernel's longest path) and tell the sweep driver which horizon a trial without
+    ``lr_total_steps`` gets (``info["lr_horizon"]``)."""
+    from polyaxon_amd.ops import lr_schedule as lrs
+
+    kind = _lr_schedule(params)
+    if kind:
+        mode = str(params.get("lr_horizon", "max"))
+        lrs.horizon_steps(mode, 1, 1, 1)  # rejects an unknown mode when the program is built
+        prog.hp_keys = prog.hp_keys + lrs.KEYS
+        prog.info["warm_hparams"] = {**prog.info.get("warm_hparams", {}), "lr_schedule": "cosine", "warmup_steps": 1,
+                                     "lr_total_steps": 4, "min_lr_ratio": 0.1}
+        prog.info["lr_schedule"] = kind
+        prog.info["lr_horizon"] = mode
+    return prog
+
+
+def lr_horizon(prog) -> Optional[str]:
+    """The program's ``lr_horizon`` mode when it has a schedule, else None (ops/lr_schedule.py with_horizon)."""
+    return (getattr(prog, "info", None) or {}).get("lr_horizon")
 
 
 def _resnet(params: Dict[str, Any], device, tiny: bool) -> TrialProgram:
@@ -82,14 +125,14 @@ def _resnet(params: Dict[str, Any], device, tiny: bool) -> TrialProgram:
     model = resnet18ish(num_classes=classes) if tiny else resnet50(num_classes=classes)
     clip = _clip_grad(params)
     ex = ResidentTrialExecutor(model, data, dev, optimizer="sgd", use_graph=bool(params.get("graph", False)),
-                               clip_grad=clip)
-    return _with_clip(TrialProgram(
+                               clip_grad=clip, lr_schedule=_lr_schedule(params))
+    return _with_schedule(_with_clip(TrialProgram(
         ex, unit_steps=int(params.get("unit_steps", 1 if tiny else 4)),
         window=int(params.get("window", 4)), hp_keys=("lr", "momentum", "weight_decay", "nesterov"),
         info={"model": "resnet18ish" if tiny else "resnet50", "batch": batch, "image": image,
               "classes": classes, "data": "synthetic, fresh per step (ops/synth.py)",
               "warm_hparams": {"lr": 0.01, "momentum": 0.9, "weight_decay": 1e-4},
-              "images_per_step": batch}), clip)
+              "images_per_step": batch}), clip), params)
 
 
 def _mlp(params: Dict[str, Any], device) -> TrialProgram:
@@ -105,12 +148,12 @@ def _mlp(params: Dict[str, Any], device) -> TrialProgram:
     y = (x @ torch.randn(784, 10, generator=g)).argmax(1)
     clip = _clip_grad(params)
     ex = ResidentTrialExecutor(MLP(), (x, y), dev, optimizer="sgd", use_graph=dev.type == "cuda", channels_last=False,
-                               clip_grad=clip)
-    return _with_clip(TrialProgram(
+                               clip_grad=clip, lr_schedule=_lr_schedule(params))
+    return _with_schedule(_with_clip(TrialProgram(
         ex, unit_steps=int(params.get("unit_steps", 10)), window=int(params.get("window", 4)),
         hp_keys=("lr", "momentum", "weight_decay"),
         info={"model": "mlp", "batch": bs, "warm_hparams": {"lr": 0.01, "momentum": 0.9},
-              "images_per_step": bs}), clip)
+              "images_per_step": bs}), clip), params)
 
 
 def _gpt2(params: Dict[str, Any], device, tiny: bool) -> TrialProgram:
@@ -146,8 +189,8 @@ def _gpt2(params: Dict[str, Any], device, tiny: bool) -> TrialProgram:
     clip = _clip_grad(params)
     ex = ResidentTrialExecutor(model, data, dev, loss_fn=lm_loss, optimizer="adamw",
                                use_graph=bool(params.get("graph", False)), channels_last=False,
-                               lp_dtype=torch.bfloat16, clip_grad=clip)
-    return _with_clip(TrialProgram(
+                               lp_dtype=torch.bfloat16, clip_grad=clip, lr_schedule=_lr_schedule(params))
+    return _with_schedule(_with_clip(TrialProgram(
         ex, unit_steps=int(params.get("unit_steps", 4 if tiny else 10)),
         window=int(params.get("window", 4)),
         hp_keys=("lr", "beta1", "beta2", "eps", "weight_decay"),
@@ -157,7 +200,7 @@ def _gpt2(params: Dict[str, Any], device, tiny: bool) -> TrialProgram:
                                "weight_decay": 0.1},
               "tokens_per_step": batch * seq, "floor_loss": data.floor_loss,
               "unigram_loss": data.unigram_loss, "chance_loss": data.chance_loss,
-              "active_vocab": data.active_vocab}), clip)
+              "active_vocab": data.active_vocab}), clip), params)
 
 
 PROGRAMS: Dict[str, Callable[[Dict[str, Any], Any], TrialProgram]] = {

@@ -151,6 +151,7 @@ class _FixedBudget:
 
     def __init__(self, units: float):
         self.units = units
+        self.max_iter = units  # the LR-schedule horizon of a fixed-budget trial is its own step count
 
     def get_n_resources_for_iteration(self, iteration: int, rung: int) -> float:
         return self.units
@@ -543,6 +544,17 @@ class ResidentWorker:
             for cid, v in sh.results[rung].items():
                 self.asha_metrics.values[row0 + rung, cols.index(cid)] = v
 
+    def _trial_hparams(self, params: Dict[str, Any], max_resource: float, r: float) -> Dict[str, Any]:
+        """The hyper-parameters of a trial's declarations; a program with an LR schedule gets ``lr_total_steps``
+        from its ``lr_horizon`` (``max``: the bracket's / shard's maximum resource; ``rung``: this rung's) when the
+        declarations name none.  A BO batch is a one-rung bracket of ``units``: its horizon is the trial's own step
+        count under either mode."""
+        from polyaxon_amd.ops import lr_schedule as lrs
+        from polyaxon_amd.polyflow.programs import lr_horizon
+
+        hp = {k: v for k, v in params.items() if k in self.program.hp_keys}
+        return lrs.with_horizon(hp, lr_horizon(self.program), max_resource, r, self.program.unit_steps)
+
     def run_round(self, chan: Channel) -> None:
         import torch
 
@@ -586,7 +598,7 @@ class ResidentWorker:
                 else:
                     ex.reset(seed=(br.seed * 1000003 + br.iteration * 1009 + cid) & 0x7FFFFFFF)
                     steps = int(round(r * self.program.unit_steps))
-                ex.set_hparams(**{k: v for k, v in params.items() if k in self.program.hp_keys})
+                ex.set_hparams(**self._trial_hparams(params, m.max_iter, r))
                 ex.run(steps)
                 ex.commit(self.metrics.values[row], slot, self.program.window)
                 if br.resume and more:
@@ -625,7 +637,7 @@ class ResidentWorker:
             else:
                 ex.reset(seed=(sh.seed * 1000003 + cid) & 0x7FFFFFFF)
                 steps = int(round(r * self.program.unit_steps))
-            ex.set_hparams(**{k: v for k, v in params.items() if k in self.program.hp_keys})
+            ex.set_hparams(**self._trial_hparams(params, sh.max_r, r))
             ex.run(steps)
             ex.commit(self.asha_metrics.values[sh.row0 + rung], col, self.program.window)
             if rung < sh.n_rungs - 1 and self._snapshot_room():

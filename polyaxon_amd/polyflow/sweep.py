@@ -24,6 +24,7 @@ from typing import Callable, Dict, List, Optional
 import torch
 
 from polyaxon_amd.obs.tracing import trace_range
+from polyaxon_amd.ops import lr_schedule as lrs
 from polyaxon_amd.polytune.kernels import BracketMetrics
 from polyaxon_amd.polytune.managers import HyperbandIterationConfig, HyperbandSearchManager
 
@@ -51,7 +52,15 @@ class SweepResult:
 
 class HyperbandSweep:
     def __init__(self, manager: HyperbandSearchManager, executor, unit_steps: int, hp_keys=None,
-                 seed: int = 0, metric_window: int = 4, on_trial_end: Optional[Callable] = None):
+                 seed: int = 0, metric_window: int = 4, on_trial_end: Optional[Callable] = None,
+                 lr_horizon: str = "max"):
+        """``lr_horizon``: on an executor with an LR schedule, the ``lr_total_steps`` of a trial whose params name
+        none (ops/lr_schedule.py horizon_steps).  ``max``: ``max_iter x unit_steps``, one curve for the whole sweep
+        that a resumed promotion continues along; ``rung``: the rung's cumulative resource, so every rung anneals
+        fully -- with ``resume: true`` a promotion is then a warm restart (its step counter continues, its LR jumps
+        back up onto the longer curve)."""
+        lrs.horizon_steps(lr_horizon, 1, 1, 1)  # rejects an unknown mode
+        self.lr_horizon = lr_horizon if getattr(executor.opt, "scheduled", False) else None
         self.manager = manager
         self.ex = executor
         self.unit_steps = unit_steps
@@ -89,6 +98,7 @@ class HyperbandSweep:
             self.ex.reset(seed=self.seed * 100003 + cid)
             steps = int(round(r * self.unit_steps))
         hp = {k: v for k, v in params.items() if k != self.resource_name}
+        hp = lrs.with_horizon(hp, self.lr_horizon, self.manager.max_iter, r, self.unit_steps)
         self.ex.set_hparams(**hp)
         self.ex.run(steps)
         self.ex.commit(self.metrics.values[0], slot, self.window)

@@ -51,6 +51,25 @@ def _parser(name: str) -> argparse.ArgumentParser:
     return ap
 
 
+def _schedule_args(ap: argparse.ArgumentParser, warmup: bool) -> None:
+    """The device-resident LR schedule (ops/optim.py) of the resnet and lm trainers; ``none``: constant ``--lr``."""
+    ap.add_argument("--lr_schedule", default="none",
+                    choices=["none", "constant", "linear", "cosine", "step", "inv_sqrt"],
+                    help="LR schedule evaluated on the device from the step counter, --lr being its base LR and the "
+                         "run's step count its horizon; none = off: the optimizer is built without a schedule")
+    ap.add_argument("--min_lr_ratio", type=float, default=0.0, help="schedule floor as a fraction of --lr")
+    ap.add_argument("--lr_decay_gamma", type=float, default=0.1, help="step schedule: factor per decay")
+    ap.add_argument("--lr_decay_every", type=int, default=1, help="step schedule: steps between decays")
+    if warmup:
+        ap.add_argument("--warmup_steps", type=int, default=0, help="linear warm-up steps of the schedule")
+
+
+def _schedule_hparams(args, total_steps: int) -> dict:
+    return {"lr_schedule": args.lr_schedule, "warmup_steps": args.warmup_steps, "lr_total_steps": total_steps,
+            "min_lr_ratio": args.min_lr_ratio, "lr_decay_gamma": args.lr_decay_gamma,
+            "lr_decay_every": args.lr_decay_every}
+
+
 def _parse(ap: argparse.ArgumentParser, argv):
     args = ap.parse_args(argv)
     args._defaults = {a.dest: a.default for a in ap._actions}
@@ -136,14 +155,18 @@ def train_resnet(argv=None) -> float:
     ap.add_argument("--image", type=int, default=224)
     ap.add_argument("--units", type=int, default=1)
     ap.add_argument("--unit_steps", type=int, default=8)
+    _schedule_args(ap, warmup=True)
     args = _parse(ap, argv)
     dev = _device(args)
     g = torch.Generator().manual_seed(args.seed)
-    x = torch.randn(args.bs, 3, args.image, args.image, generator=g).to(torch.bfloat16)
+    x = torch.randn(args.bs, 3, args.image, args.image, generator=g)
+    if dev.type == "cuda":  # the CPU path has no autocast: its fp32 weights take an fp32 batch
+        x = x.to(torch.bfloat16)
     x = x.contiguous(memory_format=torch.channels_last)
     y = torch.randint(0, 1000, (args.bs,), generator=g)
     clip = args.max_grad_norm > 0
-    ex = ResidentTrialExecutor(resnet50(), (x, y), dev, use_graph=False, clip_grad=clip)
+    sched = args.lr_schedule != "none"
+    ex = ResidentTrialExecutor(resnet50(), (x, y), dev, use_graph=False, clip_grad=clip, lr_schedule=sched)
     ckpt = _ckpt_path() if args.ckpt else None
     done_units = 0
     ex.reset(seed=args.seed)
@@ -157,6 +180,8 @@ def train_resnet(argv=None) -> float:
     # (the executor passes on only what its optimizer knows: max_grad_norm exists when clipping is on)
     ex.set_hparams(lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay,
                    max_grad_norm=args.max_grad_norm)
+    if sched:  # the horizon is the trial's full resource: a RESUMEd rung continues the curve at its restored step
+        ex.set_hparams(**_schedule_hparams(args, args.units * args.unit_steps))
     ex.run(max(0, args.units - done_units) * args.unit_steps)
     out = torch.full((1,), float("nan"), device=dev)
     ex.commit(out, 0, window=4)
@@ -165,10 +190,11 @@ def train_resnet(argv=None) -> float:
         torch.save({"params": ex.flat.params, "momentum": ex.opt.momentum_buf, "buffers": ex.buffers,
                     "step": int(ex.step.item()), "units": args.units}, ckpt)
     xp = _tracker()
+    lr_out = {"lr": float(ex.current_lr())} if sched else {}
     if xp is not None:
-        xp.log_metrics(step=int(ex.step.item()), loss=loss)
+        xp.log_metrics(step=int(ex.step.item()), loss=loss, **lr_out)
         xp.close()
-    print(json.dumps({"loss": loss, "units": args.units}))
+    print(json.dumps({"loss": loss, "units": args.units, **lr_out}))
     return loss
 
 
@@ -203,8 +229,10 @@ def train_lm(argv=None) -> float:
     ap.add_argument("--zero1", action="store_true",
                     help="ZeRO-1: reduce-scatter each gradient bucket, AdamW on this rank's 1/W slice inside the "
                          "backward, all-gather the bf16 weights (parallel/ddp.py); also PLX_ZERO1=1")
+    _schedule_args(ap, warmup=False)  # --warmup_steps above: host-side without a schedule, the schedule's with one
     args = _parse(ap, argv)
     clip = args.max_grad_norm > 0
+    sched = args.lr_schedule != "none"
     if clip and (args.zero1 or os.environ.get("PLX_ZERO1", "0") == "1"
                  or os.environ.get("PLX_OPT_IN_BACKWARD", "0") == "1"):
         ap.error("--max_grad_norm needs the whole gradient before any update: it cannot be combined with --zero1 / "
@@ -238,7 +266,10 @@ def train_lm(argv=None) -> float:
         flat.enable_direct_grads(True)  # weight-gradient GEMMs write into the flat bf16 grads (ops/lm.py)
     step = torch.zeros(1, dtype=torch.int32, device=dev)
     opt = FusedAdamW(flat, lr=args.lr, betas=(0.9, args.beta2), weight_decay=args.weight_decay, step_counter=step,
-                     max_grad_norm=args.max_grad_norm if clip else None)
+                     max_grad_norm=args.max_grad_norm if clip else None,
+                     lr_schedule=args.lr_schedule if sched else None)
+    if sched:  # evaluated on the device every step from `step`: no per-step set_hparams below
+        opt.set_hparams(**_schedule_hparams(args, args.steps))
     # PLX_OPT_IN_BACKWARD=1: the AdamW update of each gradient bucket runs inside the backward as the bucket completes
     # (parallel/ddp.py).  Off by default: bitwise the same trajectory, but on one MI355X the HBM-bound update only
     # moved time from itself to the backward's memory-bound kernels (Llama-3 8B 18.17k vs 18.03k tokens/s with a
@@ -275,8 +306,9 @@ def train_lm(argv=None) -> float:
             if dev.type == "cuda":
                 torch.cuda.synchronize(dev)
             t0 = time.time()
-        lr = args.lr * min(1.0, (it + 1) / args.warmup_steps) if args.warmup_steps else args.lr
-        opt.set_hparams(lr=lr)
+        if not sched:
+            lr = args.lr * min(1.0, (it + 1) / args.warmup_steps) if args.warmup_steps else args.lr
+            opt.set_hparams(lr=lr)
         if it and not args.fixed_batch:
             tokens = batch()
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
@@ -290,6 +322,8 @@ def train_lm(argv=None) -> float:
             if xp is not None and (it + 1) % args.log_every == 0:
                 # the norm of the averaged gradients is the same on every rank: no reduction of its own
                 extra = {"grad_norm": opt.grad_norm().clone()} if clip else {}
+                if sched:
+                    extra["lr"] = opt.current_lr().clone()
                 xp.log_metrics(step=it + 1, loss=loss_mean[0], **extra)
             if it == args.steps - 1:
                 loss_val = float(loss_mean[0])
@@ -309,6 +343,8 @@ def train_lm(argv=None) -> float:
         if clip:
             cs = opt.clip_stats()
             clip_out = {"grad_norm": cs["grad_norm"], "skipped_steps": int(cs["skipped"])}
+        if sched:
+            clip_out["lr"] = float(opt.current_lr())
         print(json.dumps({"loss": loss_val, "tokens_per_s": round(tok_s, 1), "world": info["world"], **clip_out,
                           "ms_per_step": round(dt / max(1, args.steps - skip) * 1e3, 3),
                           "host_ms_per_step": round(t_host / max(1, args.steps - skip) * 1e3, 3),
