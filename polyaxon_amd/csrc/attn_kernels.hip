@@ -9,7 +9,8 @@
 //                        directly the B operand of O^T += V^T . P^T (cdna_hip_programming.md §3 "accumulator tile
 //                        as the next MFMA's operand") -- P never touches LDS.  V^T fragments come from
 //                        ds_read_b64_tr_b16 transposed reads of the row-major V tile (T10).
-//   attn_bwd_dq_kernel   same orientation: S^T, dP^T = V.dO^T, dS^T = P^T*(dP^T - delta), dQ^T += K^T . dS^T.
+//   attn_bwd_dq_kernel   same orientation: S^T, dP^T = V.dO^T, dS^T = P^T*(dP^T - delta), dQ^T += K^T . dS^T;
+//                        delta = rowsum(dO * O) is the diagonal of one O.dO^T tile per wave, stored for dK/dV.
 //   attn_bwd_dkdv_kernel 128 keys / workgroup (32 per wave), sweeping every query head of its GQA group and every
 //                        query tile: S = Q.K^T, dP = dO.V^T (query rows in registers: the log-sum-exp and delta of
 //                        each row are per-register constants, no reductions), dV += P^T.dO and dK += dS^T.Q with
@@ -281,31 +282,9 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd_kernel(Attn
   }
 }
 
-// ---------------------------------------------------------------------------------------- backward: delta
-// delta[b][h][q] = sum_d dO . O   (16 lanes per row, 8 elements each)
-template <int D>
-__global__ __launch_bounds__(NT) void attn_bwd_delta_kernel(AttnArgs a) {
-  constexpr int LPR = D / 8;  // lanes per row
-  const long long rows = (long long)a.B * a.H * a.S;
-  const long long row = ((long long)blockIdx.x * NT + threadIdx.x) / LPR;
-  const int part = threadIdx.x % LPR;
-  float acc = 0.f;
-  if (row < rows) {
-    const int q = (int)(row % a.S);
-    const long long bh = row / a.S;
-    const int b = (int)(bh / a.H), hh = (int)(bh % a.H);
-    const bf16x8 o = *(const bf16x8*)(a.o + b * a.so.b + hh * a.so.h + (long long)q * a.so.s + part * 8);
-    const bf16x8 g = *(const bf16x8*)(a.dout + b * a.sdo.b + hh * a.sdo.h + (long long)q * a.sdo.s + part * 8);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc += (float)o[j] * (float)g[j];
-  }
-#pragma unroll
-  for (int off = LPR / 2; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
-  if (row < rows && part == 0) a.delta[row] = acc;
-}
-
 // ------------------------------------------------------------------------------------------- backward: dQ
-// NW waves x 32 queries per workgroup: the K / V tile in LDS serves NW * 32 query rows (see the forward)
+// NW waves x 32 queries per workgroup: the K / V tile in LDS serves NW * 32 query rows (see the forward).  Also
+// produces delta[b][h][q] = sum_d dO . O of its rows (read from the stored bf16 O) for itself and the dK/dV kernel.
 template <int D, int NW>
 __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_bwd_dq_kernel(AttnArgs a) {
   constexpr int QB = 32 * NW, TB = 64 * 2 * D, STAGE = 2 * TB, ND = D / 32, NS = D / 16;
@@ -320,17 +299,33 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_bwd_dq_kernel(A
   stage_tile<D, 64, NW>(smem, K, a.sk.s, a.Skv, a.zero, wave, lane);
   stage_tile<D, 64, NW>(smem + TB, V, a.sv.s, a.Skv, a.zero, wave, lane);
   bf16x8 qf[NS], gf[NS];
+  // delta[q] = dO[q] . O[q] is the diagonal of the wave's O . dO^T tile, summed by the same MFMA chain (same k order,
+  // same operand slots) as dP^T = V . dO^T below: where a row's softmax is one probability of 1 (O = that V row) the
+  // two are the same fp32 number and dS = p (dP - delta) cancels exactly, which a separately ordered sum does not.
+  f32x16 dl = zero16();
   {
     const __bf16* qr = a.q + blk.b * a.sq.b + blk.hq * a.sq.h + (long long)qc * a.sq.s + 8 * h;
     const __bf16* gr = a.dout + blk.b * a.sdo.b + blk.hq * a.sdo.h + (long long)qc * a.sdo.s + 8 * h;
+    const __bf16* orow = a.o + blk.b * a.so.b + blk.hq * a.so.h + (long long)qc * a.so.s + 8 * h;
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
       qf[s] = *(const bf16x8*)(qr + 16 * s);
       gf[s] = *(const bf16x8*)(gr + 16 * s);
+      dl = mfma(*(const bf16x8*)(orow + 16 * s), gf[s], dl);
     }
   }
+  // row ql of column ql sits in register (ql & 3) + 4 (ql >> 3) of lane half (ql >> 2) & 1 (acc_row)
+  float dlt = 0.f;
+#pragma unroll
+  for (int r = 0; r < 16; ++r)
+    if (r == (ql & 3) + 4 * (ql >> 3)) dlt = dl[r];
+  {
+    const float other = __shfl_xor(dlt, 32);
+    if (h != ((ql >> 2) & 1)) dlt = other;
+  }
   const long long srow = ((long long)blk.b * a.H + blk.hq) * a.S + qc;
-  const float lse2 = a.lse2[srow], dlt = a.delta[srow], c = a.c;
+  const float lse2 = a.lse2[srow], c = a.c;
+  if (qi < a.S && h == 0) a.delta[srow] = dlt;  // for the dK/dV kernel, which runs after this one
   f32x16 dq[ND];
 #pragma unroll
   for (int dt = 0; dt < ND; ++dt) dq[dt] = zero16();
@@ -756,12 +751,10 @@ int launch_bwd(const AttnArgs& a, float* ws, hipStream_t stream) {
   static int once = prepare(attn_bwd_dq_kernel<D, 4>, QLDS) | prepare(attn_bwd_dq_kernel<D, 8>, QLDS) |
                     prepare(attn_bwd_dkdv_kernel<D>, KLDS) | prepare(attn_bwd_dkdv8_kernel<D>, KLDS8);
   if (once) return once;
-  const long long rows = (long long)a.B * a.H * a.S;
   const int qb = 32 * g_dq_waves;
   const int qgrid = ((a.S + qb - 1) / qb) * a.H * a.B;
   const int kgrid = ((a.Skv + 127) / 128) * a.H * a.B;
-  hipLaunchKernelGGL(attn_bwd_delta_kernel<D>, dim3((unsigned)((rows * (D / 8) + NT - 1) / NT)), dim3(NT), 0, stream,
-                     a);
+  // the dQ kernel goes first: it writes delta, which the dK/dV kernel reads
   if (g_dq_waves == 4) hipLaunchKernelGGL((attn_bwd_dq_kernel<D, 4>), dim3(qgrid), dim3(256), QLDS, stream, a);
   else hipLaunchKernelGGL((attn_bwd_dq_kernel<D, 8>), dim3(qgrid), dim3(512), QLDS, stream, a);
   if (g_dkdv_waves == 8)

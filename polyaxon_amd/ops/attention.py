@@ -4,7 +4,7 @@
 ``flash_attention(q, k, v)`` takes head-major ``[B, H, S, D]`` / ``[B, Hkv, S, D]`` tensors (what ops/lm.qkv_rope
 produces) and returns the output already in ``[B, S, H, D]`` order -- the layout the output projection reads --
 so no transpose copy follows attention.  Backward recomputes the probabilities from the saved log-sum-exp
-(FlashAttention-2): a row-dot kernel for delta = rowsum(dO * O), a dQ kernel and a dK/dV kernel that owns a
+(FlashAttention-2): a dQ kernel, which also produces delta = rowsum(dO * O), and a dK/dV kernel that owns a
 128-key block x one query head (fp32 per-head partials summed over the GQA group by a reduce kernel;
 no atomics).
 
