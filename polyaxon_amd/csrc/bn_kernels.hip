@@ -888,6 +888,291 @@ __global__ __launch_bounds__(256) void stem_pool_bn_bwd_kernel(const bf16x8* __r
   }
 }
 
+// ---- thinned stem kernels (g_bn_thin): the same arithmetic per element as the three kernels above
+// A/B knob (PLX_BN_THIN, plx_bn_set_thin): 1 = the thinned kernels serve the stem's forward / backward passes
+// (stem_*_thin_kernel), 0 = their predecessors.  Both give bit-identical results.
+int g_bn_thin = 1;
+
+// Per-channel constants of the thinned kernels, staged once per block in LDS as float4 [array][half][group]: a thread
+// reads the 4 channels (half h of its group's 8) of one array with one conflict-free 16-byte read (consecutive lanes,
+// consecutive groups), just before it uses them, so no constant stays in a register across the loop.
+__device__ __forceinline__ int thin_slot(int arr, int k, int grp, int ngrp) {
+  return ((arr * 2 + (k >> 2)) * ngrp + grp) * 4 + (k & 3);
+}
+
+// Keeps the LDS reads of a loop trip inside the trip: hipcc would otherwise hoist them (loop invariant) and hold
+// every constant in registers again.
+__device__ __forceinline__ void thin_trip_fence() { asm volatile("" ::: "memory"); }
+
+// Pins four registers at this point of the program: what is computed from them cannot move above it, what they
+// were computed from cannot sink below it.
+__device__ __forceinline__ void thin_pin4(uint32_t& a, uint32_t& b, uint32_t& c, uint32_t& d) {
+  asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
+}
+
+// Keeps hipcc's scheduler from interleaving the channel pairs (or window taps) of a trip: each is scheduled on its
+// own, in program order, so the temporaries of one are dead before the next begins.
+__device__ __forceinline__ void thin_sched_fence() { __builtin_amdgcn_sched_barrier(0); }
+
+constexpr int kStemFwdRows = 8;  // output rows a block of the thinned forward walks down
+constexpr int kStemDxRows = 4;   // quad rows per block of the thinned dx pass
+
+// bf16(relu(x * a + b)) of a pixel's 8 channels, packed as the apply pass would store them
+__device__ __forceinline__ uint4 stem_tf(const uint4 q, const float* a, const float* b) {
+  const uint32_t qw[4] = {q.x, q.y, q.z, q.w};
+  uint32_t r[4];
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    const float lo = fmaxf(fmaf(__uint_as_float(qw[w] << 16), a[2 * w], b[2 * w]), 0.f);
+    const float hi = fmaxf(fmaf(__uint_as_float(qw[w] & 0xffff0000u), a[2 * w + 1], b[2 * w + 1]), 0.f);
+    r[w] = (uint32_t)f2bf(lo) | ((uint32_t)f2bf(hi) << 16);
+  }
+  return make_uint4(r[0], r[1], r[2], r[3]);
+}
+
+// one window tap of stem_apply_pool_kernel's max: `none` (no valid tap so far) is that kernel's arg[k] == 255,
+// which is the same for all 8 channels, so it is kept once per thread
+__device__ __forceinline__ void stem_tap(const uint4 f4, bool ok, bool& none, uint32_t t9, float* best, uint32_t* arg) {
+  const uint32_t fw[4] = {f4.x, f4.y, f4.z, f4.w};
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const float f = __uint_as_float((k & 1) ? (fw[k >> 1] & 0xffff0000u) : (fw[k >> 1] << 16));
+    if (ok && (f > best[k] || none)) {
+      best[k] = f;
+      arg[k] = t9;
+    }
+  }
+  none = none && !ok;
+  thin_sched_fence();
+}
+
+// stem_apply_pool_kernel with every input pixel transformed once per column of windows instead of once per window:
+// a thread owns output column ow (8 channels) and walks down kStemFwdRows output rows of one image; input row
+// 2 * oh + 1 is the last row of window oh and the first of window oh + 1, so its transformed values are carried over
+// (6 loads and transforms per output instead of 9), and the next trip's loads are issued before this trip's math.
+// Grid: gx * N * cpi blocks, gx = ceil(OW * G / 256) column chunks x cpi = ceil(OH / kStemFwdRows) row chunks per image.
+__global__ __launch_bounds__(256) void stem_apply_pool_thin_kernel(const bf16x8* __restrict__ x,
+                                                                   const float* __restrict__ sb,
+                                                                   bf16x8* __restrict__ y, u8x8* __restrict__ idx,
+                                                                   int H, int W, int G, int OH, int OW, int gx,
+                                                                   int cpi) {
+  const unsigned bx = blockIdx.x % (unsigned)gx, chunk = blockIdx.x / (unsigned)gx;
+  const unsigned j = bx * 256u + threadIdx.x;
+  if (j >= (unsigned)(OW * G)) return;
+  const unsigned g = j % (unsigned)G, ow = j / (unsigned)G;
+  const int C = G * 8;
+  float a[8], b[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    a[k] = sb[g * 8 + k];
+    b[k] = sb[C + g * 8 + k];
+  }
+  const int n = (int)chunk / cpi, oh0 = ((int)chunk - n * cpi) * kStemFwdRows;
+  const int oh1 = oh0 + kStemFwdRows < OH ? oh0 + kStemFwdRows : OH;
+  // the window's 3 columns: clamped (always valid) addresses, out-of-image taps are skipped in the max
+  int col[3];
+  bool cok[3];
+#pragma unroll
+  for (int kw = 0; kw < 3; ++kw) {
+    const int iw = (int)ow * 2 - 1 + kw;
+    cok[kw] = iw >= 0 && iw < W;
+    col[kw] = (iw < 0 ? 0 : (iw >= W ? W - 1 : iw)) * G;
+  }
+  const bf16x8* xn = x + (size_t)n * H * W * G + g;
+  uint4 pr[3], q[6];  // transformed row 2 * oh - 1 (unused at oh = 0: never valid there); rows 2 * oh, 2 * oh + 1
+  {
+    const int ihp = oh0 > 0 ? 2 * oh0 - 1 : 0, ihb = 2 * oh0 + 1 < H ? 2 * oh0 + 1 : H - 1;
+#pragma unroll
+    for (int kw = 0; kw < 3; ++kw) {
+      pr[kw] = *(const uint4*)(xn + (size_t)ihp * W * G + col[kw]);
+      q[kw] = *(const uint4*)(xn + (size_t)(2 * oh0) * W * G + col[kw]);
+      q[3 + kw] = *(const uint4*)(xn + (size_t)ihb * W * G + col[kw]);
+    }
+#pragma unroll
+    for (int kw = 0; kw < 3; ++kw) pr[kw] = stem_tf(pr[kw], a, b);
+  }
+  for (int oh = oh0; oh < oh1; ++oh) {
+    uint4 nq[6];  // the next trip's rows (the last trip reloads its own)
+    {
+      const int ohn = oh + 1 < oh1 ? oh + 1 : oh, ihb = 2 * ohn + 1 < H ? 2 * ohn + 1 : H - 1;
+#pragma unroll
+      for (int kw = 0; kw < 3; ++kw) {
+        nq[kw] = *(const uint4*)(xn + (size_t)(2 * ohn) * W * G + col[kw]);
+        nq[3 + kw] = *(const uint4*)(xn + (size_t)ihb * W * G + col[kw]);
+      }
+    }
+    float best[8];
+    uint32_t arg[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      best[k] = -INFINITY;
+      arg[k] = 255;
+    }
+    bool none = true;
+    const bool r0 = oh > 0, r2 = 2 * oh + 1 < H;  // row 2 * oh is always inside the image
+#pragma unroll
+    for (int kw = 0; kw < 3; ++kw) stem_tap(pr[kw], r0 && cok[kw], none, kw, best, arg);
+#pragma unroll
+    for (int kw = 0; kw < 3; ++kw) stem_tap(stem_tf(q[kw], a, b), cok[kw], none, 3 + kw, best, arg);
+#pragma unroll
+    for (int kw = 0; kw < 3; ++kw) {
+      pr[kw] = stem_tf(q[3 + kw], a, b);
+      stem_tap(pr[kw], r2 && cok[kw], none, 6 + kw, best, arg);
+    }
+    bf16x8 o;
+    u8x8 m;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      o.v[k] = f2bf(best[k]);
+      m.v[k] = (uint8_t)arg[k];
+    }
+    const size_t t = (size_t)(n * OH + oh) * OW * G + j;
+    y[t] = o;
+    idx[t] = m;
+#pragma unroll
+    for (int e = 0; e < 6; ++e) q[e] = nq[e];
+  }
+}
+
+// stem_pool_bn_bwd_kernel<DX> with the per-channel constants in LDS (thin_slot: a | b | A | B | D for the dx pass,
+// a | b | mean | invstd for the partials pass), read per half group (4 channels) right before their use, and the
+// channels as the outer loop of a quad, so a quad's loads die half by half.  Per channel the 4 pixels are still taken
+// in the order e = 0..3.  DX = false: the grid, the block -> quad-row assignment (by, by + rows_y, ...), each thread's
+// accumulation order, the LDS sum and the partial layout are those of stem_pool_bn_bwd_kernel<false>.  DX = true:
+// grid (ceil(QW * G / 256), ceil(rows / kStemDxRows)), a block takes kStemDxRows consecutive quad rows.
+// Dynamic LDS: (DX ? 5 : 4) * C floats.
+template <bool DX>
+__global__ __launch_bounds__(256) void stem_pool_bn_bwd_thin_kernel(
+    const bf16x8* __restrict__ dy, const u8x8* __restrict__ idx, const bf16x8* __restrict__ x,
+    const float* __restrict__ sb, const float* __restrict__ mean, const float* __restrict__ invstd,
+    const float* __restrict__ coef, bf16x8* __restrict__ dx, float* __restrict__ part, int N, int H, int W, int G,
+    int OH, int OW) {
+  extern __shared__ float4 thin_lds[];
+  constexpr int NA = DX ? 5 : 4;
+  const int QH = (H + 1) / 2, QW = (W + 1) / 2;
+  const unsigned j0 = blockIdx.x * 256u + threadIdx.x;
+  const bool active = j0 < (unsigned)(QW * G);
+  const unsigned j = active ? j0 : 0u;
+  const unsigned g = j % (unsigned)G;                     // == threadIdx.x % G (256 % G == 0)
+  const int qb = (int)(j / (unsigned)G);
+  const int C = G * 8;
+  for (int e = threadIdx.x; e < NA * C; e += 256) {
+    const int arr = e / C, c = e - arr * C;
+    const float* src = arr == 0 ? sb : arr == 1 ? sb + C : DX ? coef + (arr - 2) * C : arr == 2 ? mean : invstd;
+    ((float*)thin_lds)[thin_slot(arr, c & 7, c >> 3, G)] = src[c];
+  }
+  __syncthreads();
+  float s1[8], s2[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) s1[k] = s2[k] = 0.f;
+  const int rows = N * QH;
+  const int row0 = DX ? blockIdx.y * kStemDxRows : blockIdx.y, step = DX ? 1 : gridDim.y;
+  const int row1 = DX ? (row0 + kStemDxRows < rows ? row0 + kStemDxRows : rows) : rows;
+  for (int row = row0; active && row < row1; row += step) {
+    thin_trip_fence();
+    const int n = row / QH, qa = row - n * QH;
+    // windows (qa + p, qb + q) and the quad's pixels: whole-vector loads from clamped addresses, all issued before
+    // any use; validity is applied per element
+    uint2 am[4];
+    uint4 d[4], xq[4];
+    bool pv[4];
+#pragma unroll
+    for (int p = 0; p < 2; ++p)
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        const int w4 = p * 2 + q, oh = qa + p, ow = qb + q;
+        const size_t off = ((size_t)(n * OH + (oh < OH ? oh : OH - 1)) * OW + (ow < OW ? ow : OW - 1)) * G + g;
+        am[w4] = *(const uint2*)(idx + off);
+        d[w4] = *(const uint4*)(dy + off);
+        if (!(oh < OH && ow < OW)) am[w4] = make_uint2(0xffffffffu, 0xffffffffu);  // no tap code (0..8) matches 0xff
+        const int ih = 2 * qa + p, iw = 2 * qb + q;         // quad pixel (di, dj) = (p, q)
+        pv[w4] = ih < H && iw < W;
+        xq[w4] = *(const uint4*)(x + ((size_t)(n * H + (ih < H ? ih : H - 1)) * W + (iw < W ? iw : W - 1)) * G + g);
+      }
+    uint32_t amw[4][2], dw[4][4], xw[4][4];
+#pragma unroll
+    for (int w4 = 0; w4 < 4; ++w4) {
+      amw[w4][0] = am[w4].x, amw[w4][1] = am[w4].y;
+      dw[w4][0] = d[w4].x, dw[w4][1] = d[w4].y, dw[w4][2] = d[w4].z, dw[w4][3] = d[w4].w;
+      xw[w4][0] = xq[w4].x, xw[w4][1] = xq[w4].y, xw[w4][2] = xq[w4].z, xw[w4][3] = xq[w4].w;
+    }
+    uint32_t ow4[4][4];  // dx of the quad's 4 pixels, packed
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      float cst[NA][4];
+#pragma unroll
+      for (int arr = 0; arr < NA; ++arr) {
+        const float4 v = thin_lds[(arr * 2 + h) * G + g];
+        cst[arr][0] = v.x, cst[arr][1] = v.y, cst[arr][2] = v.z, cst[arr][3] = v.w;
+      }
+      thin_pin4(amw[0][h], amw[1][h], amw[2][h], amw[3][h]);
+#pragma unroll
+      for (int kp = 0; kp < 2; ++kp) {  // a channel pair = one register of every load
+        const int w = h * 2 + kp;
+        thin_pin4(dw[0][w], dw[1][w], dw[2][w], dw[3][w]);
+        thin_pin4(xw[0][w], xw[1][w], xw[2][w], xw[3][w]);
+#pragma unroll
+        for (int k2 = 0; k2 < 2; ++k2) {
+          const int kk = kp * 2 + k2, k = h * 4 + kk;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int di = e >> 1, dj = e & 1;
+            float acc = 0.f;
+#pragma unroll
+            for (int p = 0; p < 2; ++p)
+#pragma unroll
+              for (int q = 0; q < 2; ++q) {
+                const int kh = di + 1 - 2 * p, kw = dj + 1 - 2 * q;   // this pixel's tap in window (p, q)
+                if (kh < 0 || kw < 0) continue;                      // compile-time
+                const int w4 = p * 2 + q;
+                const uint32_t ab = amw[w4][h] >> (8 * kk) & 0xffu;
+                const float dv = __uint_as_float(k2 ? (dw[w4][w] & 0xffff0000u) : (dw[w4][w] << 16));
+                acc += ab == (uint32_t)(kh * 3 + kw) ? dv : 0.f;   // invalid windows' bytes were set to 0xff
+              }
+            const float xf = __uint_as_float(k2 ? (xw[e][w] & 0xffff0000u) : (xw[e][w] << 16));
+            // rounded to bf16 as the unfused pool backward stores it (a plain cast: one v_cvt_pk_bf16_f32, RNE)
+            const float dz = (pv[e] && fmaf(xf, cst[0][kk], cst[1][kk]) > 0.f) ? (float)(__bf16)acc : 0.f;
+            if constexpr (DX) {
+              const uint32_t ob = f2bf(fmaf(cst[2][kk], dz, fmaf(cst[3][kk], xf, cst[NA - 1][kk])));
+              ow4[e][w] = k2 ? (ow4[e][w] | (ob << 16)) : ob;
+            } else {
+              s1[k] += dz;
+              s2[k] = fmaf(dz, (xf - cst[2][kk]) * cst[3][kk], s2[k]);
+            }
+          }
+        }
+        if constexpr (DX) thin_pin4(ow4[0][w], ow4[1][w], ow4[2][w], ow4[3][w]);  // formed here, not at the stores
+        thin_sched_fence();
+      }
+    }
+    if constexpr (DX) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (pv[e])
+          *(uint4*)(dx + ((size_t)(n * H + 2 * qa + (e >> 1)) * W + 2 * qb + (e & 1)) * G + g) =
+              make_uint4(ow4[e][0], ow4[e][1], ow4[e][2], ow4[e][3]);
+    }
+  }
+  if constexpr (!DX) {
+    // the 256 / G threads of this block that share channel group g: fixed-order sum through LDS
+    __shared__ float red[256 * 17];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      red[threadIdx.x * 17 + k] = s1[k];
+      red[threadIdx.x * 17 + 8 + k] = s2[k];
+    }
+    __syncthreads();
+    const int nb = gridDim.x * gridDim.y, blk = blockIdx.y * gridDim.x + blockIdx.x;
+    for (int e = threadIdx.x; e < G * 16; e += 256) {     // e = (value v, group gg)
+      const int gg = e % G, v = e / G;
+      float sum = 0.f;
+      for (int r = gg; r < 256; r += G) sum += red[r * 17 + v];
+      const int c = gg * 8 + (v & 7);
+      part[((int64_t)(v < 8 ? 0 : nb) + blk) * C + c] = sum;
+    }
+  }
+}
+
 // over quad rows: pass 1 (partials) a few per block (rows_y <= g_stem_bwd_cap bounds the level-1 partials: 4096 rows
 // ~4 MB at the stem's shape), pass 2 (dx) one per block.
 constexpr int g_stem_bwd_cap = 4096;
@@ -898,6 +1183,9 @@ inline dim3 stem_bwd_grid(int N, int H, int W, int G, bool dx) {
 }
 
 }  // namespace
+
+// A/B knob: 1 (default) = the thinned stem kernels, 0 = their predecessors (g_bn_thin)
+PLX_API void plx_bn_set_thin(int on) { g_bn_thin = on != 0; }
 
 // fp32 workspace the host must pass as `partials`: level-1 [2][nblk][C] + level-2 [2][S][C].
 PLX_API int64_t plx_bn_workspace(int64_t M, int C) {
@@ -1078,6 +1366,13 @@ PLX_API int plx_stem_bn_pool_forward(const void* x, void* y, void* idx, int N, i
   if (rc) return rc;
   const int OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
   const int rows = N * OH;
+  if (g_bn_thin) {
+    const int gx = (OW * G + 255) / 256, cpi = (OH + kStemFwdRows - 1) / kStemFwdRows;
+    if ((int64_t)gx * N * cpi > 0x7fffffff) return 1;
+    hipLaunchKernelGGL(stem_apply_pool_thin_kernel, dim3(gx * N * cpi), dim3(256), 0, stream, (const bf16x8*)x,
+                       scale_bias, (bf16x8*)y, (u8x8*)idx, H, W, G, OH, OW, gx, cpi);
+    return (int)hipGetLastError();
+  }
   hipLaunchKernelGGL(stem_apply_pool_kernel, dim3((OW * G + 255) / 256, rows < 65535 ? rows : 65535), dim3(256), 0,
                      stream, (const bf16x8*)x, scale_bias, (bf16x8*)y, (u8x8*)idx, N, H, W, G, OH, OW);
   return (int)hipGetLastError();
@@ -1102,6 +1397,24 @@ PLX_API int plx_stem_bn_pool_backward(const void* dy, const void* idx, const voi
   const int OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
   const dim3 grid = stem_bwd_grid(N, H, W, G, false), grid_dx = stem_bwd_grid(N, H, W, G, true);
   const int nblk = grid.x * grid.y;
+  if (g_bn_thin) {
+    const int rows = N * ((H + 1) / 2);
+    const dim3 grid_thin(grid.x, (rows + kStemDxRows - 1) / kStemDxRows);
+    hipLaunchKernelGGL(stem_pool_bn_bwd_thin_kernel<false>, grid, dim3(256), sizeof(float) * 4 * C, stream,
+                       (const bf16x8*)dy, (const u8x8*)idx, (const bf16x8*)x, scale_bias, save_mean, save_invstd,
+                       (const float*)nullptr, (bf16x8*)nullptr, workspace, N, H, W, G, OH, OW);
+    reduce_finalize_bwd(stream, workspace, nblk, workspace + 2 * (int64_t)nblk * C, counters,
+                        BwdFin{C, (int64_t)N * H * W, gamma, save_mean, save_invstd, dgamma, dbeta, coef, accumulate});
+    if (grid_thin.y <= 65535)
+      hipLaunchKernelGGL(stem_pool_bn_bwd_thin_kernel<true>, grid_thin, dim3(256), sizeof(float) * 5 * C, stream,
+                         (const bf16x8*)dy, (const u8x8*)idx, (const bf16x8*)x, scale_bias, save_mean, save_invstd,
+                         coef, (bf16x8*)dx, (float*)nullptr, N, H, W, G, OH, OW);
+    else  // more quad-row chunks than a grid's y extent: the predecessor loops over rows
+      hipLaunchKernelGGL(stem_pool_bn_bwd_kernel<true>, grid_dx, dim3(256), 0, stream, (const bf16x8*)dy,
+                         (const u8x8*)idx, (const bf16x8*)x, scale_bias, save_mean, save_invstd, coef, (bf16x8*)dx,
+                         (float*)nullptr, N, H, W, G, OH, OW);
+    return (int)hipGetLastError();
+  }
   hipLaunchKernelGGL(stem_pool_bn_bwd_kernel<false>, grid, dim3(256), 0, stream, (const bf16x8*)dy, (const u8x8*)idx,
                      (const bf16x8*)x, scale_bias, save_mean, save_invstd, (const float*)nullptr, (bf16x8*)nullptr,
                      workspace, N, H, W, G, OH, OW);

@@ -190,6 +190,8 @@ def lib(name: str) -> ctypes.CDLL:
         _declare(name, handle)
         if name == "plx_conv" and os.environ.get("PLX_WGRAD_ATOMIC"):  # A/B knob: 0 = slab reducer (deterministic)
             handle.plx_set_tn_atomic(int(os.environ["PLX_WGRAD_ATOMIC"]))
+        if name == "plx_bn" and os.environ.get("PLX_BN_THIN"):  # A/B knob: 0 = the kernels before the thinned ones
+            handle.plx_bn_set_thin(int(os.environ["PLX_BN_THIN"]))
         if name == "plx_gemm" and os.environ.get("PLX_GEMM_WAVES"):  # 8 = ping-pong kernel, 4 = AGPR 4-wave kernel
             handle.plx_gemm256_set_waves(int(os.environ["PLX_GEMM_WAVES"]))
         _loaded[name] = handle
@@ -226,6 +228,7 @@ SIGNATURES: Dict[str, Dict[str, list]] = {
         "plx_set_adamw_wide": [_I],
     },
     "plx_bn": {
+        "plx_bn_set_thin": [_I],
         "plx_bn_workspace": [_L, _I],
         "plx_bn_forward": [_P, _P, _P, _L, _I, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P],
         "plx_bn_apply": [_P, _P, _P, _L, _I, _P, _I, _P],
@@ -375,7 +378,7 @@ SIGNATURES: Dict[str, Dict[str, list]] = {
 }
 
 
-RESTYPES: Dict[str, object] = {"plx_attn_bwd_workspace": ctypes.c_longlong, "plx_conv_wgrad_workspace": _L, "plx_bn_workspace": _L, "plx_bn_l2_workspace": _L, "plx_partial_colsum_workspace": _L, "plx_stem_bn_pool_bwd_workspace": _L, "plx_gemm_tn_workspace": _L, "plx_gemm256_sk_ws": ctypes.c_longlong, "plx_stem_conv_wgrad_workspace": _L, "plx_pm_create": _P, "plx_pm_destroy": None, "plx_set_tn_v2": None, "plx_set_tn2_stem": None, "plx_set_tn2_c64": None, "plx_set_tn_atomic": None, "plx_set_adamw_grid_cap": None, "plx_set_adamw_wide": None, "plx_attn_set_fwd_waves": None, "plx_attn_set_dq_waves": None, "plx_attn_set_dkdv_waves": None, "plx_gemm256_set_split_target": None,
+RESTYPES: Dict[str, object] = {"plx_attn_bwd_workspace": ctypes.c_longlong, "plx_conv_wgrad_workspace": _L, "plx_bn_workspace": _L, "plx_bn_l2_workspace": _L, "plx_partial_colsum_workspace": _L, "plx_stem_bn_pool_bwd_workspace": _L, "plx_gemm_tn_workspace": _L, "plx_gemm256_sk_ws": ctypes.c_longlong, "plx_stem_conv_wgrad_workspace": _L, "plx_pm_create": _P, "plx_pm_destroy": None, "plx_set_tn_v2": None, "plx_set_tn2_stem": None, "plx_set_tn2_c64": None, "plx_set_tn_atomic": None, "plx_bn_set_thin": None, "plx_set_adamw_grid_cap": None, "plx_set_adamw_wide": None, "plx_attn_set_fwd_waves": None, "plx_attn_set_dq_waves": None, "plx_attn_set_dkdv_waves": None, "plx_gemm256_set_split_target": None,
                                "plx_pm_wake": None, "plx_rccl_init": _P, "plx_rccl_error": ctypes.c_char_p}
 
 
