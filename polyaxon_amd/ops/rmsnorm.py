@@ -162,6 +162,11 @@ def rms_norm(x: torch.Tensor, weight: torch.Tensor, eps: float = 1e-5) -> torch.
 
 
 def layer_norm_reference(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, eps: float) -> torch.Tensor:
+    if x.is_cuda and x.dtype != weight.dtype:
+        # the types the fused path takes (bf16 rows, fp32 parameters) at a width it does not: F.layer_norm on the GPU
+        # wants one dtype and raises outside autocast; fp32 math and the input's dtype out, as rms_norm_reference
+        y = torch.nn.functional.layer_norm(x.float(), (x.shape[-1],), weight.float(), bias.float(), eps)
+        return y.to(x.dtype)
     return torch.nn.functional.layer_norm(x, (x.shape[-1],), weight, bias, eps)
 
 
