@@ -11,13 +11,17 @@
 // lane t / Gb, so its per-channel state (shift, scale, bias, mean, invstd) stays in registers while it
 // walks rows; one wave reads 64 x 16 B = 1 KiB contiguous per instruction.
 //
-//   plx_bn_fwd_stats     per-block shifted sum / sum-of-squares partials  [nblk, C] (+ level-2 reduce)
-//   plx_bn_fwd_finalize  mean, invstd, fused scale/bias, running-stat update (unbiased var)
-//   plx_bn_fwd_apply     y = act(x*scale + bias [+ res])
-//   plx_bn_bwd_reduce    partial sums of dz and dz*xhat   (dz = dy * [y > 0] when act)
-//   plx_bn_bwd_finalize  dgamma, dbeta and the dx coefficients  dx = A*dz + B*x + D
-//   plx_bn_bwd_dx        dx (and d_residual = dz) in one pass, optionally with the reduction partials of the
-//                        BatchNorm that produced the residual (ResBn: a downsampling branch's BN skips its reduce)
+//   bn_stats_kernel                per-block shifted sum / sum-of-squares partials [2][nblk][C]
+//   bn_fwd_reduce_finalize_kernel  level-2 reduce, then mean, invstd, fused scale/bias, running stats (unbiased var)
+//   bn_apply_kernel                y = act(x*scale + bias [+ res]), and the 1-bit ReLU mask
+//   bn_bwd_reduce_kernel           partial sums of dz and dz*xhat   (dz = dy * [y > 0] when act)
+//   bn_bwd_reduce_finalize_kernel  level-2 reduce, then dgamma, dbeta and the dx coefficients  dx = A*dz + B*x + D
+//   bn_bwd_dx_kernel               dx (and d_residual = dz) in one pass, optionally with the reduction partials of the
+//                                  BatchNorm that produced the residual (ResBn: a downsampling branch's BN skips its
+//                                  reduce)
+//   (without a counter array a reduce + finalize is bn_partial_reduce_kernel + bn_{fwd,bwd}_finalize_kernel)
+// Entry points: plx_bn_forward / plx_bn_backward (one argument struct each), plx_bn_apply, plx_bn_apply_res_relu, the
+// stem's plx_stem_bn_pool_forward / _backward (stem_*_kernel), and the size queries (plx_bn_workspace, ...).
 #include <hip/hip_runtime.h>
 
 #include "handoff.h"
@@ -509,7 +513,7 @@ __global__ __launch_bounds__(NT) void bn_bwd_finalize_kernel(const float* __rest
 // The BatchNorm that produced this one's residual input (a ResNet downsampling branch), when d_residual is that
 // BatchNorm's complete gradient: the dx pass also reduces its per-block partials  sum dz2  and
 // sum dz2 * (x2 - mean2) * invstd2  (dz2 = d_residual, masked by its own ReLU if it had one) into
-// part[2][gridDim.x][C], so that BatchNorm's backward skips its reduce pass (plx_bn_backward_from_partials).
+// part[2][gridDim.x][C], so that BatchNorm's backward skips its reduce pass (plx_bn_backward with ext_part).
 struct ResBn {
   const bf16x8* x;
   const uint8_t* mask;   // nullptr: no ReLU
@@ -604,7 +608,7 @@ struct Plan {
 };
 
 inline bool plan_for(int64_t M, int C, Plan* p) {
-  if (C <= 0 || (C & 7)) return false;
+  if (M < 1 || C <= 0 || (C & 7)) return false;  // M < 1 first: rows_per_block would be 0, and nblk divides by it
   const int G = C / 8;
   if (G & (G - 1)) return false;  // power of two channel groups
   p->G = G;
@@ -1187,59 +1191,116 @@ inline dim3 stem_bwd_grid(int N, int H, int W, int G, bool dx) {
 // A/B knob: 1 (default) = the thinned stem kernels, 0 = their predecessors (g_bn_thin)
 PLX_API void plx_bn_set_thin(int on) { g_bn_thin = on != 0; }
 
-// fp32 workspace the host must pass as `partials`: level-1 [2][nblk][C] + level-2 [2][S][C].
+// fp32 workspace of a call that runs its own statistics / reduce pass: level-1 [2][nblk][C] + level-2 [2][S][C].
 PLX_API int64_t plx_bn_workspace(int64_t M, int C) {
   Plan p;
   if (!plan_for(M, C, &p)) return -1;
   return 2 * (int64_t)(p.nblk + p.S) * C;
 }
 
-PLX_API int plx_bn_forward(const void* x, const void* res, void* y, int64_t M, int C, const float* gamma,
-                           const float* beta, float eps, float momentum, float* running_mean, float* running_var,
-                           float* save_mean, float* save_invstd, float* scale_bias /* [2C] */,
-                           float* partials /* plx_bn_workspace floats */, uint8_t* mask /* M*C/8 bytes or null */,
-                           int relu, const float* res_sb /* nullable [2C], see bn_apply_kernel */,
-                           unsigned* counters /* nullable: >= ceil(C/64) zeroed words, one launch for
-                                                 reduce + finalize */,
-                           hipStream_t stream) {
-  Plan p;
-  if (!plan_for(M, C, &p) || M < 1) return 1;
-  float* psum = partials;
-  float* psq = partials + (int64_t)p.nblk * C;
-  hipLaunchKernelGGL(bn_stats_kernel, dim3(p.nblk, p.gy), dim3(kBlock), 0, stream, (const bf16x8*)x, M, p.G, p.Gb,
-                     p.rows_per_block, psum, psq);
-  float* l2 = partials + 2 * (int64_t)p.nblk * C;
-  reduce_finalize_fwd(stream, partials, p.nblk, l2, counters,
-                      FwdFin{(const uint16_t*)x, C, M, gamma, beta, eps, momentum, running_mean, running_var,
-                             save_mean, save_invstd, scale_bias, scale_bias + C});
-  const int64_t n_vec = M * p.G;
-  if (y != nullptr)  // y == nullptr: statistics and scale/bias only (the apply is deferred to the consumer)
-    launch_apply(stream, n_vec, p.G, x, res, y, scale_bias, scale_bias + C, relu, relu ? mask : nullptr, res_sb);
-  return (int)hipGetLastError();
-}
-
-// Level-2 workspace for externally produced level-1 partials ([2][nblk][C], e.g. from the 1x1-conv GEMM
-// epilogue, csrc/conv_gemm.hip): 2 * ceil(nblk / 64) * C floats.
+// fp32 workspace of a call that is given level-1 partials ([2][nblk][C], e.g. from the 1x1-conv GEMM epilogue,
+// csrc/conv_gemm.hip): the level-2 rows only, 2 * ceil(nblk / 64) * C floats.
 PLX_API int64_t plx_bn_l2_workspace(int nblk, int C) {
   return 2 * (int64_t)((nblk + kRowsPerSplit - 1) / kRowsPerSplit) * C;
 }
 
-// Forward with the per-channel sums already produced by the op that wrote x (unshifted sums over nblk row
-// blocks): skips the stats pass over x.  l2 holds plx_bn_l2_workspace(nblk, C) floats.
-PLX_API int plx_bn_forward_from_partials(const void* x, const void* res, void* y, int64_t M, int C,
-                                         const float* gamma, const float* beta, float eps, float momentum,
-                                         float* running_mean, float* running_var, float* save_mean,
-                                         float* save_invstd, float* scale_bias, const float* partials, int nblk,
-                                         float* l2, uint8_t* mask, int relu, const float* res_sb,
-                                         unsigned* counters, hipStream_t stream) {
+// Row blocks of the dx pass = the nblk of the residual-BatchNorm partials it writes (ResBn).
+PLX_API int plx_bn_dx_blocks(int64_t M, int C) {
   Plan p;
-  if (!plan_for(M, C, &p) || M < 1 || nblk < 1) return 1;
-  reduce_finalize_fwd(stream, partials, nblk, l2, counters,
-                      FwdFin{nullptr, C, M, gamma, beta, eps, momentum, running_mean, running_var, save_mean,
-                             save_invstd, scale_bias, scale_bias + C});
-  const int64_t n_vec = M * p.G;
-  if (y != nullptr)
-    launch_apply(stream, n_vec, p.G, x, res, y, scale_bias, scale_bias + C, relu, relu ? mask : nullptr, res_sb);
+  if (!plan_for(M, C, &p)) return -1;
+  return apply_grid(M * p.G, p.G);
+}
+
+// Arguments of plx_bn_forward / plx_bn_backward (host images: ops/_native.py BnForwardArgs / BnBackwardArgs, their
+// sizes compared with plx_bn_args_size at load).  Common to both:
+//   ext_part == nullptr: the call runs its own statistics / reduce pass over x into `workspace`
+//                        (plx_bn_workspace(M, C) floats)
+//   ext_part given:      level-1 partials [2][ext_nblk][C] from the op that wrote x (forward: unshifted sum, sum of
+//                        squares) or dy (backward: sum dz, sum dz*xhat); no pass over x, and `workspace` holds only
+//                        the level-2 rows (plx_bn_l2_workspace(ext_nblk, C) floats)
+//   counters (nullable): >= ceil(C/64) zeroed words, reduce + finalize then run as one launch
+struct BnForwardArgs {
+  const void *x, *res;    // res nullable: residual added before the activation
+  void* y;                // nullptr: statistics and scale/bias only (the apply is deferred to the consumer)
+  int64_t M;
+  int C, relu;
+  const float *gamma, *beta;
+  float eps, momentum;
+  float *running_mean, *running_var;  // nullable (both)
+  float *save_mean, *save_invstd, *scale_bias /* [2C] */, *workspace;
+  const float* ext_part;
+  int ext_nblk;
+  uint8_t* mask;          // M*C/8 bytes, written when relu (nullable: no mask wanted)
+  const float* res_sb;    // nullable [2C], see bn_apply_kernel
+  unsigned* counters;
+};
+
+struct BnBackwardArgs {
+  const void* x;
+  const uint8_t* mask;    // the forward's ReLU bit mask: required when relu and a pass reads it
+  const void* dy;
+  void* dx;               // nullptr: reduce + finalize only (dgamma, dbeta, coef): dx = coef[0] * dz + coef[1] * x +
+                          // coef[2] is then formed by the data-gradient GEMM that consumes it (plx_gemm_nt_bndx)
+  void* dres;             // nullable: d_residual = dz, written by the dx pass
+  int64_t M;
+  int C, relu;
+  const float *gamma, *save_mean, *save_invstd;
+  float *dgamma, *dbeta, *coef /* [3C] */, *workspace;
+  const float* ext_part;
+  int ext_nblk, accumulate;  // accumulate: dgamma / dbeta += (else =)
+  ResBn resbn;            // all null: none; else needs dres
+  unsigned* counters;
+};
+
+PLX_API int plx_bn_args_size(int backward) {
+  return (int)(backward ? sizeof(BnBackwardArgs) : sizeof(BnForwardArgs));
+}
+
+PLX_API int plx_bn_forward(const BnForwardArgs* a, hipStream_t stream) {
+  Plan p;
+  const int C = a->C;
+  if (!plan_for(a->M, C, &p) || (a->ext_part != nullptr && a->ext_nblk < 1)) return 1;
+  const bool own = a->ext_part == nullptr;  // this call runs the statistics pass itself
+  const int nblk = own ? p.nblk : a->ext_nblk;
+  float* l2 = own ? a->workspace + 2 * (int64_t)nblk * C : a->workspace;
+  if (own)
+    hipLaunchKernelGGL(bn_stats_kernel, dim3(p.nblk, p.gy), dim3(kBlock), 0, stream, (const bf16x8*)a->x, a->M, p.G,
+                       p.Gb, p.rows_per_block, a->workspace, a->workspace + (int64_t)nblk * C);
+  // x_row0: the own pass sums x shifted by its first row; external partials are unshifted sums
+  reduce_finalize_fwd(stream, own ? a->workspace : a->ext_part, nblk, l2, a->counters,
+                      FwdFin{own ? (const uint16_t*)a->x : nullptr, C, a->M, a->gamma, a->beta, a->eps, a->momentum, a->running_mean,
+                             a->running_var, a->save_mean, a->save_invstd, a->scale_bias, a->scale_bias + C});
+  if (a->y != nullptr)
+    launch_apply(stream, a->M * p.G, p.G, a->x, a->res, a->y, a->scale_bias, a->scale_bias + C, a->relu,
+                 a->relu ? a->mask : nullptr, a->res_sb);
+  return (int)hipGetLastError();
+}
+
+PLX_API int plx_bn_backward(const BnBackwardArgs* a, hipStream_t stream) {
+  Plan p;
+  const int C = a->C, relu = a->relu;
+  const ResBn& rb = a->resbn;
+  const bool has_rb = rb.x != nullptr || rb.mask != nullptr || rb.mean != nullptr || rb.invstd != nullptr ||
+                      rb.part != nullptr;
+  if (!plan_for(a->M, C, &p) || (a->ext_part != nullptr && a->ext_nblk < 1)) return 1;
+  // the reduce and the dx pass read the mask; with external partials and no dx pass nothing does
+  if (relu && a->mask == nullptr && (a->ext_part == nullptr || a->dx != nullptr)) return 1;
+  if (has_rb && (a->dres == nullptr || rb.part == nullptr || rb.x == nullptr || rb.mean == nullptr ||
+                 rb.invstd == nullptr))
+    return 1;
+  if (a->dx == nullptr && (a->dres != nullptr || has_rb)) return 1;
+  const bool own = a->ext_part == nullptr;  // this call runs the reduce pass itself
+  const int nblk = own ? p.nblk : a->ext_nblk;
+  float* l2 = own ? a->workspace + 2 * (int64_t)nblk * C : a->workspace;
+  if (own)
+    hipLaunchKernelGGL(relu ? bn_bwd_reduce_kernel<true> : bn_bwd_reduce_kernel<false>, dim3(p.nblk, p.gy),
+                       dim3(kBlock), 0, stream, (const bf16x8*)a->x, a->mask, (const bf16x8*)a->dy, a->M, p.G, p.Gb,
+                       p.rows_per_block, a->save_mean, a->save_invstd, relu, a->workspace,
+                       a->workspace + (int64_t)nblk * C);
+  reduce_finalize_bwd(stream, own ? a->workspace : a->ext_part, nblk, l2, a->counters,
+                      BwdFin{C, a->M, a->gamma, a->save_mean, a->save_invstd, a->dgamma, a->dbeta, a->coef,
+                             a->accumulate});
+  if (a->dx != nullptr) launch_dx(stream, a->M * p.G, p.G, a->x, a->mask, a->dy, a->dx, a->dres, a->coef, relu, rb);
   return (int)hipGetLastError();
 }
 
@@ -1264,85 +1325,6 @@ PLX_API int plx_bn_apply_res_relu(const void* x, const void* res, void* y, int64
   return (int)hipGetLastError();
 }
 
-// mask: the ReLU bit mask written by the forward (required when relu); accumulate: dgamma/dbeta += (else =)
-// Row blocks of the dx pass = the nblk of the residual-BatchNorm partials it writes (ResBn, plx_bn_backward*).
-PLX_API int plx_bn_dx_blocks(int64_t M, int C) {
-  Plan p;
-  if (!plan_for(M, C, &p)) return -1;
-  return apply_grid(M * p.G, p.G);
-}
-
-PLX_API int plx_bn_backward(const void* x, const uint8_t* mask, const void* dy, void* dx, void* dres, int64_t M, int C,
-                            const float* gamma, const float* save_mean, const float* save_invstd, float* dgamma,
-                            float* dbeta, float* coef /* [3C] */, float* partials /* plx_bn_workspace floats */, int relu,
-                            int accumulate, const ResBn* resbn /* nullable, needs dres */, unsigned* counters,
-                            hipStream_t stream) {
-  Plan p;
-  if (!plan_for(M, C, &p) || M < 1 || (relu && mask == nullptr)) return 1;
-  if (resbn != nullptr && (dres == nullptr || resbn->part == nullptr)) return 1;
-  const ResBn rb = resbn != nullptr ? *resbn : ResBn{};
-  float* pa = partials;
-  float* pb = partials + (int64_t)p.nblk * C;
-  hipLaunchKernelGGL(relu ? bn_bwd_reduce_kernel<true> : bn_bwd_reduce_kernel<false>, dim3(p.nblk, p.gy), dim3(kBlock), 0, stream, (const bf16x8*)x,
-                     mask, (const bf16x8*)dy, M, p.G, p.Gb, p.rows_per_block, save_mean, save_invstd,
-                     relu, pa, pb);
-  float* l2 = partials + 2 * (int64_t)p.nblk * C;
-  reduce_finalize_bwd(stream, partials, p.nblk, l2, counters,
-                      BwdFin{C, M, gamma, save_mean, save_invstd, dgamma, dbeta, coef, accumulate});
-  const int64_t n_vec = M * p.G;
-  launch_dx(stream, n_vec, p.G, x, mask, dy, dx, dres, coef, relu, rb);
-  return (int)hipGetLastError();
-}
-
-// Backward whose per-block partials ([2][nblk][C]: sum dz, sum dz*xhat) were produced by the op that wrote dy
-// (the data-gradient GEMM epilogue, csrc/conv_gemm.hip BnBwd): skips the reduce pass over x and dy.  l2 holds
-// plx_bn_l2_workspace(nblk, C) floats.
-PLX_API int plx_bn_backward_from_partials(const void* x, const uint8_t* mask, const void* dy, void* dx, void* dres,
-                                          int64_t M, int C, const float* gamma, const float* save_mean,
-                                          const float* save_invstd, float* dgamma, float* dbeta, float* coef,
-                                          const float* partials, int nblk, float* l2, int relu, int accumulate,
-                                          const ResBn* resbn, unsigned* counters, hipStream_t stream) {
-  Plan p;
-  if (!plan_for(M, C, &p) || M < 1 || nblk < 1 || (relu && mask == nullptr)) return 1;
-  if (resbn != nullptr && (dres == nullptr || resbn->part == nullptr)) return 1;
-  const ResBn rb = resbn != nullptr ? *resbn : ResBn{};
-  reduce_finalize_bwd(stream, partials, nblk, l2, counters,
-                      BwdFin{C, M, gamma, save_mean, save_invstd, dgamma, dbeta, coef, accumulate});
-  const int64_t n_vec = M * p.G;
-  launch_dx(stream, n_vec, p.G, x, mask, dy, dx, dres, coef, relu, rb);
-  return (int)hipGetLastError();
-}
-
-// Reduce + finalize only (dgamma, dbeta, coef), no dx pass: for a BatchNorm whose dx = coef[0] * dz + coef[1] * x +
-// coef[2] is produced by the data-gradient GEMM that consumes it (csrc/conv_gemm.hip plx_gemm_nt_bndx).  Arguments
-// as plx_bn_backward / plx_bn_backward_from_partials.
-PLX_API int plx_bn_backward_coef(const void* x, const uint8_t* mask, const void* dy, int64_t M, int C,
-                                 const float* gamma, const float* save_mean, const float* save_invstd, float* dgamma,
-                                 float* dbeta, float* coef, float* partials, int relu, int accumulate,
-                                 unsigned* counters, hipStream_t stream) {
-  Plan p;
-  if (!plan_for(M, C, &p) || M < 1 || (relu && mask == nullptr)) return 1;
-  float* pa = partials;
-  float* pb = partials + (int64_t)p.nblk * C;
-  hipLaunchKernelGGL(relu ? bn_bwd_reduce_kernel<true> : bn_bwd_reduce_kernel<false>, dim3(p.nblk, p.gy), dim3(kBlock), 0, stream, (const bf16x8*)x,
-                     mask, (const bf16x8*)dy, M, p.G, p.Gb, p.rows_per_block, save_mean, save_invstd,
-                     relu, pa, pb);
-  reduce_finalize_bwd(stream, partials, p.nblk, partials + 2 * (int64_t)p.nblk * C, counters,
-                      BwdFin{C, M, gamma, save_mean, save_invstd, dgamma, dbeta, coef, accumulate});
-  return (int)hipGetLastError();
-}
-
-PLX_API int plx_bn_backward_coef_from_partials(int64_t M, int C, const float* gamma, const float* save_mean,
-                                               const float* save_invstd, float* dgamma, float* dbeta, float* coef,
-                                               const float* partials, int nblk, float* l2, int accumulate,
-                                               unsigned* counters, hipStream_t stream) {
-  Plan p;
-  if (!plan_for(M, C, &p) || M < 1 || nblk < 1) return 1;
-  reduce_finalize_bwd(stream, partials, nblk, l2, counters,
-                      BwdFin{C, M, gamma, save_mean, save_invstd, dgamma, dbeta, coef, accumulate});
-  return (int)hipGetLastError();
-}
-
 // ---- ResNet stem BatchNorm + ReLU + 3x3/s2/p1 max-pool (see stem_apply_pool_kernel)
 // Forward: statistics (workspace `partials`: plx_bn_workspace(N*H*W, C) floats) -> mean / invstd / scale|bias ->
 // y [N][OH][OW][C] bf16 and idx [N*OH*OW*C] window positions.
@@ -1355,14 +1337,11 @@ PLX_API int plx_stem_bn_pool_forward(const void* x, void* y, void* idx, int N, i
                                      hipStream_t stream) {
   const int G = C / 8;
   if (N <= 0 || H <= 0 || W <= 0 || C % 8 || G > 256 || 256 % G) return 1;
-  const int rc = ext_part != nullptr
-                     ? plx_bn_forward_from_partials(x, nullptr, nullptr, (int64_t)N * H * W, C, gamma, beta, eps,
-                                                    momentum, running_mean, running_var, save_mean, save_invstd,
-                                                    scale_bias, ext_part, ext_nblk, partials, nullptr, 1, nullptr,
-                                                    counters, stream)
-                     : plx_bn_forward(x, nullptr, nullptr, (int64_t)N * H * W, C, gamma, beta, eps, momentum,
-                                      running_mean, running_var, save_mean, save_invstd, scale_bias, partials, nullptr,
-                                      1, nullptr, counters, stream);
+  // statistics and scale/bias only: no res, y or mask
+  const BnForwardArgs a{x, nullptr, nullptr, (int64_t)N * H * W, C, /*relu*/ 1, gamma, beta, eps, momentum,
+                        running_mean, running_var, save_mean, save_invstd, scale_bias, partials, ext_part, ext_nblk,
+                        /*mask*/ nullptr, /*res_sb*/ nullptr, counters};
+  const int rc = plx_bn_forward(&a, stream);
   if (rc) return rc;
   const int OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
   const int rows = N * OH;
@@ -1377,8 +1356,6 @@ PLX_API int plx_stem_bn_pool_forward(const void* x, void* y, void* idx, int N, i
                      stream, (const bf16x8*)x, scale_bias, (bf16x8*)y, (u8x8*)idx, N, H, W, G, OH, OW);
   return (int)hipGetLastError();
 }
-
-// A/B knob: quad rows of the stem backward's partials pass (1 .. 65535; set before sizing the workspace)
 
 // floats of workspace plx_stem_bn_pool_backward needs: level-1 [2][nblk][C] + level-2 [2][S][C]
 PLX_API int64_t plx_stem_bn_pool_bwd_workspace(int N, int H, int W, int C) {

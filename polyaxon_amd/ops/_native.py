@@ -188,6 +188,11 @@ def lib(name: str) -> ctypes.CDLL:
             build(name, force=os.environ.get("PLX_NATIVE_REBUILD") == "1")
         handle = ctypes.CDLL(str(path), mode=ctypes.RTLD_GLOBAL)
         _declare(name, handle)
+        if name == "plx_bn":
+            for backward, image in enumerate((BnForwardArgs, BnBackwardArgs)):
+                if handle.plx_bn_args_size(backward) != ctypes.sizeof(image):
+                    raise RuntimeError(f"{image.__name__} layout mismatch: HIP {handle.plx_bn_args_size(backward)} vs "
+                                       f"ctypes {ctypes.sizeof(image)}")
         if name == "plx_conv" and os.environ.get("PLX_WGRAD_ATOMIC"):  # A/B knob: 0 = slab reducer (deterministic)
             handle.plx_set_tn_atomic(int(os.environ["PLX_WGRAD_ATOMIC"]))
         if name == "plx_bn" and os.environ.get("PLX_BN_THIN"):  # A/B knob: 0 = the kernels before the thinned ones
@@ -230,18 +235,13 @@ SIGNATURES: Dict[str, Dict[str, list]] = {
     "plx_bn": {
         "plx_bn_set_thin": [_I],
         "plx_bn_workspace": [_L, _I],
-        "plx_bn_forward": [_P, _P, _P, _L, _I, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P],
+        "plx_bn_args_size": [_I],
+        "plx_bn_forward": [_P, _P],  # (BnForwardArgs*, stream)
         "plx_bn_apply": [_P, _P, _P, _L, _I, _P, _I, _P],
         "plx_bn_apply_res_relu": [_P, _P, _P, _L, _I, _P, _P, _P, _P],
         "plx_bn_l2_workspace": [_I, _I],
-        "plx_bn_forward_from_partials": [_P, _P, _P, _L, _I, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P, _I, _P, _P,
-                                         _I, _P, _P, _P],
-        "plx_bn_backward": [_P, _P, _P, _P, _P, _L, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P],
+        "plx_bn_backward": [_P, _P],  # (BnBackwardArgs*, stream)
         "plx_bn_dx_blocks": [_L, _I],
-        "plx_bn_backward_from_partials": [_P, _P, _P, _P, _P, _L, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _P,
-                                          _P, _P],
-        "plx_bn_backward_coef": [_P, _P, _P, _L, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P],
-        "plx_bn_backward_coef_from_partials": [_L, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _P],
         "plx_stem_bn_pool_forward": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P, _P, _I, _P,
                                      _P],
         "plx_stem_bn_pool_bwd_workspace": [_I, _I, _I, _I],
@@ -395,7 +395,25 @@ class ResBnArgs(ctypes.Structure):
     _fields_ = [("x", _P), ("mask", _P), ("mean", _P), ("invstd", _P), ("part", _P)]
 
 
-class BnBwdArgs(ctypes.Structure):
+class BnForwardArgs(ctypes.Structure):
+    """Host image of ``BnForwardArgs`` (csrc/bn_kernels.hip), the argument of ``plx_bn_forward``; filled by
+    :func:`polyaxon_amd.ops.bn_fused.bn_forward`."""
+    _fields_ = [("x", _P), ("res", _P), ("y", _P), ("M", _L), ("C", _I), ("relu", _I), ("gamma", _P), ("beta", _P),
+                ("eps", _F), ("momentum", _F), ("running_mean", _P), ("running_var", _P), ("save_mean", _P),
+                ("save_invstd", _P), ("scale_bias", _P), ("workspace", _P), ("ext_part", _P), ("ext_nblk", _I),
+                ("mask", _P), ("res_sb", _P), ("counters", _P)]
+
+
+class BnBackwardArgs(ctypes.Structure):
+    """Host image of ``BnBackwardArgs`` (csrc/bn_kernels.hip), the argument of ``plx_bn_backward``; filled by
+    :func:`polyaxon_amd.ops.bn_fused.bn_backward`."""
+    _fields_ = [("x", _P), ("mask", _P), ("dy", _P), ("dx", _P), ("dres", _P), ("M", _L), ("C", _I), ("relu", _I),
+                ("gamma", _P), ("save_mean", _P), ("save_invstd", _P), ("dgamma", _P), ("dbeta", _P), ("coef", _P),
+                ("workspace", _P), ("ext_part", _P), ("ext_nblk", _I), ("accumulate", _I), ("resbn", ResBnArgs),
+                ("counters", _P)]
+
+
+class GemmBnBwdArgs(ctypes.Structure):
     """Host image of ``BnBwd`` (csrc/conv_gemm.hip): fused BatchNorm-backward partials in a dgrad GEMM epilogue."""
     _fields_ = [("x", _P), ("mask", _P), ("mean", _P), ("invstd", _P), ("part", _P), ("part_ld", _I),
                 ("blk_off", _I), ("skip_h", _I), ("skip_w", _I)]

@@ -8,6 +8,7 @@ With ReLU the forward also writes a 1-bit-per-element mask (1/16 of ``y``); the 
 from __future__ import annotations
 
 import ctypes
+import functools
 
 from typing import Optional
 
@@ -33,6 +34,56 @@ def _counters(dev: torch.device):
     return _native.cached(_COUNTERS, key, lambda: torch.zeros(64, dtype=torch.int32, device=dev)).data_ptr()
 
 
+@functools.lru_cache(maxsize=None)
+def _lib() -> ctypes.CDLL:
+    return _native.lib("plx_bn")  # loaded once: _native.lib takes a lock on every call
+
+
+def _p(t):
+    """Device address of a tensor; ``None`` and raw addresses pass through."""
+    return t if t is None or isinstance(t, int) else t.data_ptr()
+
+
+def _workspace(m: int, c: int, ext_part, ext_nblk: int, device) -> torch.Tensor:
+    """fp32 workspace of one call: the level-2 rows for the ``ext_nblk`` rows of external partials, else (``ext_part``
+    is ``None``) both levels of the call's own statistics / reduce pass -- the rule of csrc/bn_kernels.hip."""
+    n = (_native.size("plx_bn", "plx_bn_l2_workspace", ext_nblk, c) if ext_part is not None
+         else _native.size("plx_bn", "plx_bn_workspace", m, c))
+    if n < 0:
+        raise RuntimeError("unsupported channel count for fused BN")
+    return torch.empty(n, dtype=torch.float32, device=device)
+
+
+def bn_forward(*, x, m, c, gamma, beta, eps, momentum, save_mean, save_invstd, scale_bias, workspace, res=None,
+               y=None, relu=False, running_mean=None, running_var=None, ext_part=None, ext_nblk=0, mask=None,
+               res_sb=None, counters=None, stream=None) -> None:
+    """``plx_bn_forward`` (csrc/bn_kernels.hip ``BnForwardArgs``, which documents the fields): pointers are tensors,
+    raw addresses or ``None``.  Raises when the library refuses the call."""
+    a = _native.BnForwardArgs(
+        x=_p(x), res=_p(res), y=_p(y), M=m, C=c, relu=int(relu), gamma=_p(gamma), beta=_p(beta), eps=eps,
+        momentum=momentum, running_mean=_p(running_mean), running_var=_p(running_var), save_mean=_p(save_mean),
+        save_invstd=_p(save_invstd), scale_bias=_p(scale_bias), workspace=_p(workspace), ext_part=_p(ext_part),
+        ext_nblk=ext_nblk, mask=_p(mask), res_sb=_p(res_sb), counters=_p(counters))
+    rc = _lib().plx_bn_forward(ctypes.byref(a), _stream() if stream is None else stream)
+    _native.check(rc, "plx_bn_forward")
+
+
+def bn_backward(*, x, dy, m, c, gamma, save_mean, save_invstd, dgamma, dbeta, coef, workspace, mask=None, dx=None,
+                dres=None, relu=False, accumulate=0, ext_part=None, ext_nblk=0, resbn=None, counters=None,
+                stream=None) -> None:
+    """``plx_bn_backward`` (csrc/bn_kernels.hip ``BnBackwardArgs``); ``dx=None``: reduce + finalize only; ``resbn``:
+    a :class:`~polyaxon_amd.ops._native.ResBnArgs` or ``None``.  Raises when the library refuses the call."""
+    a = _native.BnBackwardArgs(
+        x=_p(x), mask=_p(mask), dy=_p(dy), dx=_p(dx), dres=_p(dres), M=m, C=c, relu=int(relu), gamma=_p(gamma),
+        save_mean=_p(save_mean), save_invstd=_p(save_invstd), dgamma=_p(dgamma), dbeta=_p(dbeta), coef=_p(coef),
+        workspace=_p(workspace), ext_part=_p(ext_part), ext_nblk=ext_nblk, accumulate=int(accumulate),
+        counters=_p(counters))
+    if resbn is not None:
+        a.resbn = resbn
+    rc = _lib().plx_bn_backward(ctypes.byref(a), _stream() if stream is None else stream)
+    _native.check(rc, "plx_bn_backward")
+
+
 def _cl(t: torch.Tensor) -> torch.Tensor:
     return t if t.is_contiguous(memory_format=torch.channels_last) else t.contiguous(memory_format=torch.channels_last)
 
@@ -49,16 +100,12 @@ class _BNAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var, residual, momentum, eps, relu, ext=None, box=None,
                 link=None, rlink=None, defer=False, dxsink=None, pend=None):
-        lib = _native.lib("plx_bn")
         # dxsink (ops.conv1x1.DxSink): x is a 1x1 convolution's output as is, and that convolution's data-gradient
         # GEMM can produce this BatchNorm's dx (the backward decides)
         ctx.dxsink = dxsink if x.is_contiguous(memory_format=torch.channels_last) else None
         x = _cl(x)
         n, c, h, w = x.shape
         m = n * h * w
-        ws = _native.size("plx_bn", "plx_bn_workspace", m, c)
-        if ws < 0:
-            raise RuntimeError("unsupported channel count for fused BN")
         f32 = dict(dtype=torch.float32, device=x.device)
         # defer: no apply pass -- the output aliases x and its only consumer (the residual add of a fused
         # BatchNorm) applies scale/bias on the fly (link.affine); the backward is unchanged
@@ -67,7 +114,6 @@ class _BNAct(torch.autograd.Function):
         # pend: reduce / finalize only -- y and the mask are allocated but left unwritten, and the forward GEMM of the
         # 1x1 convolution that reads y fills them (ops.conv1x1.PendingApply, handed to bn_act through the list `pend`)
         holder, pend = pend, pend is not None and relu and residual is not None and not defer
-        yp = y.data_ptr() if (y is not None and not pend) else None
         stats = torch.empty(4 * c, **f32)  # mean | invstd | scale | bias
         res_sb = None
         if residual is not None:
@@ -75,29 +121,14 @@ class _BNAct(torch.autograd.Function):
             if rl is not None and rl.affine is not None and getattr(residual, "_plx_deferred", False):
                 res_sb = rl.affine
         res = _cl(residual) if residual is not None else None
-        rsp = res_sb.data_ptr() if res_sb is not None else None
-        rm = running_mean.data_ptr() if running_mean is not None else None
-        rv = running_var.data_ptr() if running_var is not None else None
         mask = torch.empty(m * c // 8, dtype=torch.uint8, device=x.device) if relu else None
-        mp = mask.data_ptr() if mask is not None else None
-        if ext is not None:
-            # channel sums came from the producing conv's GEMM epilogue: no stats pass over x
-            part, nblk = ext
-            l2 = torch.empty(_native.size("plx_bn", "plx_bn_l2_workspace", nblk, c), **f32)
-            rc = lib.plx_bn_forward_from_partials(
-                x.data_ptr(), res.data_ptr() if res is not None else None, yp, m, c, weight.data_ptr(),
-                bias.data_ptr(), float(eps), float(momentum), rm, rv, stats.data_ptr(), stats[c:].data_ptr(),
-                stats[2 * c:].data_ptr(), part.data_ptr(), nblk, l2.data_ptr(), mp, int(relu), rsp,
-                _counters(x.device), _stream())
-            _native.check(rc, "plx_bn_forward_from_partials")
-        else:
-            partials = torch.empty(ws, **f32)
-            rc = lib.plx_bn_forward(
-                x.data_ptr(), res.data_ptr() if res is not None else None, yp, m, c,
-                weight.data_ptr(), bias.data_ptr(), float(eps), float(momentum), rm, rv,
-                stats.data_ptr(), stats[c:].data_ptr(), stats[2 * c:].data_ptr(), partials.data_ptr(), mp, int(relu),
-                rsp, _counters(x.device), _stream())
-            _native.check(rc, "plx_bn_forward")
+        # ext: channel sums from the producing conv's GEMM epilogue -- no stats pass over x
+        part, nblk = ext if ext is not None else (None, 0)
+        sp = stats.data_ptr()  # addresses of its rows below, not slices: a slice costs the host over a microsecond
+        bn_forward(x=x, res=res, y=None if pend else y, m=m, c=c, gamma=weight, beta=bias, eps=float(eps),
+                   momentum=float(momentum), running_mean=running_mean, running_var=running_var, save_mean=sp,
+                   save_invstd=sp + 4 * c, scale_bias=sp + 8 * c, workspace=_workspace(m, c, part, nblk, x.device),
+                   ext_part=part, ext_nblk=nblk, mask=mask, relu=relu, res_sb=res_sb, counters=_counters(x.device))
         ctx.save_for_backward(x, mask, weight, stats)
         ctx.pending = PendingApply(x, res, stats[2 * c:], res_sb, mask, y) if pend else None
         if pend:
@@ -107,7 +138,6 @@ class _BNAct(torch.autograd.Function):
         ctx.box = box if (box is not None and box.armed and residual is not None) else None
         if ctx.box is not None:
             ctx.box.expect = True
-        ctx.ws = ws
         # direct gradients: dgamma / dbeta accumulate into the flat gradient slots (ops.flat.direct_grad)
         gw, gb = direct_grad(weight), direct_grad(bias)
         ctx.direct = (gw, gb) if (gw is not None and gb is not None) else None
@@ -127,7 +157,6 @@ class _BNAct(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        lib = _native.lib("plx_bn")
         x, mask, weight, stats = ctx.saved_tensors
         if ctx.pending is not None:  # the mask read below was left to the consumer's GEMM (or materialize) to write
             ctx.pending.check_done()
@@ -150,54 +179,23 @@ class _BNAct(torch.autograd.Function):
             dgb = torch.empty(2 * c, **f32)
             dg_ptr, db_ptr, acc = dgb.data_ptr(), dgb[c:].data_ptr(), 0
         coef = torch.empty(3 * c, **f32)
+        # part: the consumer's dgrad epilogue already reduced dz and dz*xhat per block
         part, nblk = ctx.link.take() if ctx.link is not None else (None, 0)
-        if ctx.dxsink is not None and dres is None:
-            # only dx to write: reduce / finalize here, and the data-gradient GEMM of the convolution that produced x
-            # forms dx = coef[0]·dz + coef[1]·x + coef[2] itself, into this (still unwritten) buffer
-            if part is not None:
-                l2 = torch.empty(_native.size("plx_bn", "plx_bn_l2_workspace", nblk, c), **f32)
-                rc = lib.plx_bn_backward_coef_from_partials(
-                    m, c, weight.data_ptr(), stats.data_ptr(), stats[c:].data_ptr(), dg_ptr, db_ptr, coef.data_ptr(),
-                    part.data_ptr(), nblk, l2.data_ptr(), acc, _counters(x.device), _stream())
-                _native.check(rc, "plx_bn_backward_coef_from_partials")
-            else:
-                partials = torch.empty(ctx.ws, **f32)
-                rc = lib.plx_bn_backward_coef(
-                    x.data_ptr(), mask.data_ptr() if mask is not None else None, dy.data_ptr(), m, c,
-                    weight.data_ptr(), stats.data_ptr(), stats[c:].data_ptr(), dg_ptr, db_ptr, coef.data_ptr(),
-                    partials.data_ptr(), int(ctx.relu), acc, _counters(x.device), _stream())
-                _native.check(rc, "plx_bn_backward_coef")
-            ctx.dxsink.put(dy, x, mask if ctx.relu else None, coef, dx)
-            if ctx.box is not None:  # masked_box (dres is None): dy and the mask ride into conv1's dgrad epilogue
-                ctx.box.put_masked(dy, mask)
-            dgamma = dgb[:c] if dgb is not None else None
-            dbeta = dgb[c:] if dgb is not None else None
-            return dx, dgamma, dbeta, None, None, None, None, None, None, None, None, None, None, None, None, None
+        # only dx to write (dxsink): reduce / finalize here, and the data-gradient GEMM of the convolution that produced
+        # x forms dx = coef[0]·dz + coef[1]·x + coef[2] itself, into this (still unwritten) buffer
+        sink = ctx.dxsink if dres is None else None
         rb = None
         if ctx.rlink is not None and dres is not None:
             rl = ctx.rlink
-            nblk2 = _native.size("plx_bn", "plx_bn_dx_blocks", m, c)
-            rl.part = torch.empty(2 * nblk2 * c, **f32)
-            rl.nblk = nblk2
-            rb = _native.ResBnArgs(rl.x.data_ptr(), rl.mask.data_ptr() if rl.mask is not None else None,
-                                   rl.mean.data_ptr(), rl.invstd.data_ptr(), rl.part.data_ptr())
-        rbp = ctypes.addressof(rb) if rb is not None else None
-        if part is not None:  # the consumer's dgrad epilogue already reduced dz and dz*xhat per block
-            l2 = torch.empty(_native.size("plx_bn", "plx_bn_l2_workspace", nblk, c), **f32)
-            rc = lib.plx_bn_backward_from_partials(
-                x.data_ptr(), mask.data_ptr() if mask is not None else None, dy.data_ptr(), dx.data_ptr(),
-                dres.data_ptr() if dres is not None else None, m, c, weight.data_ptr(), stats.data_ptr(),
-                stats[c:].data_ptr(), dg_ptr, db_ptr, coef.data_ptr(), part.data_ptr(), nblk, l2.data_ptr(),
-                int(ctx.relu), acc, rbp, _counters(x.device), _stream())
-            _native.check(rc, "plx_bn_backward_from_partials")
-        else:
-            partials = torch.empty(ctx.ws, **f32)
-            rc = lib.plx_bn_backward(
-                x.data_ptr(), mask.data_ptr() if mask is not None else None, dy.data_ptr(), dx.data_ptr(),
-                dres.data_ptr() if dres is not None else None, m, c, weight.data_ptr(), stats.data_ptr(),
-                stats[c:].data_ptr(), dg_ptr, db_ptr, coef.data_ptr(), partials.data_ptr(), int(ctx.relu), acc,
-                rbp, _counters(x.device), _stream())
-            _native.check(rc, "plx_bn_backward")
+            rl.nblk = _native.size("plx_bn", "plx_bn_dx_blocks", m, c)
+            rl.part = torch.empty(2 * rl.nblk * c, **f32)
+            rb = _native.ResBnArgs(_p(rl.x), _p(rl.mask), _p(rl.mean), _p(rl.invstd), _p(rl.part))
+        bn_backward(x=x, mask=mask, dy=dy, dx=None if sink is not None else dx, dres=dres, m=m, c=c, gamma=weight,
+                    save_mean=stats, save_invstd=stats.data_ptr() + 4 * c, dgamma=dg_ptr, dbeta=db_ptr, coef=coef,
+                    workspace=_workspace(m, c, part, nblk, x.device), ext_part=part, ext_nblk=nblk, relu=ctx.relu,
+                    accumulate=acc, resbn=rb, counters=_counters(x.device))
+        if sink is not None:
+            sink.put(dy, x, mask if ctx.relu else None, coef, dx)
         if ctx.box is not None:  # the residual's gradient rides into conv1's dgrad epilogue (ops.conv1x1)
             if masked_box:
                 ctx.box.put_masked(dy, mask)

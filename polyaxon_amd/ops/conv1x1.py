@@ -78,7 +78,8 @@ def nt_stats_rows(n: int) -> int:
 
 
 def gemm_nt(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor = None, stats: torch.Tensor = None,
-            add: torch.Tensor = None, bnr: "_native.BnBwdArgs" = None, add_mask: torch.Tensor = None) -> torch.Tensor:
+            add: torch.Tensor = None, bnr: "_native.GemmBnBwdArgs" = None,
+            add_mask: torch.Tensor = None) -> torch.Tensor:
     """out[M][N] = a[M][K] · b[N][K]ᵀ, bf16 (rows may be strided, K contiguous).  ``stats`` (fp32
     [2][ceil(M / nt_stats_rows(N))][N]) receives per-block channel sums and sums of squares of ``out``;
     ``add`` (bf16 [M][N]) is summed into the product in the epilogue, only where ``add_mask`` (a ReLU's 1-bit
@@ -110,7 +111,7 @@ def gemm_nt(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor = None, stats: t
 
 def gemm_nt_bndx(g: torch.Tensor, x: torch.Tensor, mask: torch.Tensor, coef: torch.Tensor, dy: torch.Tensor,
                  b: torch.Tensor, out: torch.Tensor = None, add: torch.Tensor = None,
-                 bnr: "_native.BnBwdArgs" = None, add_mask: torch.Tensor = None) -> torch.Tensor:
+                 bnr: "_native.GemmBnBwdArgs" = None, add_mask: torch.Tensor = None) -> torch.Tensor:
     """The data gradient ``out[M][N] = dy · bᵀ`` of a 1x1 convolution whose incoming gradient ``dy[M][K]`` is a
     BatchNorm backward's dx, produced by the GEMM itself: ``dy = coef[0]·(g·mask) + coef[1]·x + coef[2]`` per
     channel, rounded to bf16 once (bit-identical to the standalone dx pass), written to ``dy`` and consumed as the
@@ -383,19 +384,19 @@ class BnLink:
         self._args = None
         self.split = 0  # > 0: the first of two GEMMs wrote rows [0, split); the strided 1x1 dgrad still owes the rest
 
-    def _args_for(self, nblk_total: int, blk_off: int) -> "_native.BnBwdArgs":
-        return _native.BnBwdArgs(self.x.data_ptr(), self.mask.data_ptr() if self.mask is not None else None,
-                                 self.mean.data_ptr(), self.invstd.data_ptr(), self.part.data_ptr(), nblk_total,
-                                 blk_off)
+    def _args_for(self, nblk_total: int, blk_off: int) -> "_native.GemmBnBwdArgs":
+        return _native.GemmBnBwdArgs(self.x.data_ptr(), self.mask.data_ptr() if self.mask is not None else None,
+                                     self.mean.data_ptr(), self.invstd.data_ptr(), self.part.data_ptr(), nblk_total,
+                                     blk_off)
 
-    def request(self, nblk: int) -> "_native.BnBwdArgs":
+    def request(self, nblk: int) -> "_native.GemmBnBwdArgs":
         c = self.x.shape[1]
         self.part = torch.empty(2 * nblk * c, dtype=torch.float32, device=self.x.device)
         self.nblk, self.split = nblk, 0
         self._args = self._args_for(nblk, 0)
         return self._args
 
-    def request_split(self, nblk1: int, nblk2: int) -> "_native.BnBwdArgs":
+    def request_split(self, nblk1: int, nblk2: int) -> "_native.GemmBnBwdArgs":
         """ResNet downsampling block: x feeds conv1 (stride-1 1x1, dgrad deferred into the box) and the stride-2 1x1
         downsample conv (dgrad adds the box's gradient at the even-even pixels).  conv1's dgrad epilogue reduces
         the pixels the strided one never touches (rows [0, nblk1), even-even pixels skipped), and the strided
@@ -408,7 +409,7 @@ class BnLink:
         self._args = a
         return a
 
-    def request_rest(self) -> "_native.BnBwdArgs":
+    def request_rest(self) -> "_native.GemmBnBwdArgs":
         a = self._args_for(self.nblk, self.split)
         self.split = 0
         self._args = a

@@ -3,7 +3,7 @@ BatchNorm dx pass, then plx_gemm_nt reading its output) against the fused GEMM t
 (plx_gemm_nt_bndx), alternating, one JSON line per shape.
 
 Both variants start from the same per-block partials and run the same reduce / finalize launch first, as the training
-step does (plx_bn_backward_from_partials vs plx_bn_backward_coef_from_partials), and both GEMMs carry the BnBwd
+step does (plx_bn_backward from external partials, with and without its dx pass), and both GEMMs carry the BnBwd
 epilogue that serves bn2.  Every repetition uses the next of several buffer sets (>= 1 GB in total per shape), so the
 256 MiB Infinity Cache cannot hold what the previous repetition touched.  Times are per-repetition device-event
 times; bytes are counted from the shapes (activations, masks and the weight once).
@@ -20,7 +20,7 @@ import torch
 sys.path.insert(0, __import__("os").path.dirname(__import__("os").path.dirname(__import__("os").path.abspath(__file__))))
 
 from polyaxon_amd.ops import _native  # noqa: E402
-from polyaxon_amd.ops.bn_fused import _counters  # noqa: E402
+from polyaxon_amd.ops.bn_fused import _counters, bn_backward  # noqa: E402
 from polyaxon_amd.ops.conv1x1 import _zero_page, nt_stats_rows  # noqa: E402
 
 SHAPES = [(802816, 256, 64), (200704, 512, 128), (50176, 1024, 256), (12544, 2048, 512)]  # (M, K, N) of conv3's dgrad
@@ -31,7 +31,7 @@ def main():
     reps = int(sys.argv[1]) if len(sys.argv) > 1 else 20
     warmup = int(sys.argv[2]) if len(sys.argv) > 2 else 3
     dev = torch.device("cuda", 0)
-    conv, bn = _native.lib("plx_conv"), _native.lib("plx_bn")
+    conv = _native.lib("plx_conv")
     st = torch.cuda.current_stream().cuda_stream
     zero, cnt = _zero_page(dev).data_ptr(), _counters(dev)
     f32 = dict(dtype=torch.float32, device=dev)
@@ -56,25 +56,22 @@ def main():
             s["mask2"] = torch.randint(0, 256, (m * n // 8,), device=dev, dtype=torch.uint8)
             s["dy"] = torch.empty(m, k, device=dev, dtype=torch.bfloat16)
             s["c"] = torch.empty(m, n, device=dev, dtype=torch.bfloat16)
-            s["bnr"] = _native.BnBwdArgs(s["x2"].data_ptr(), s["mask2"].data_ptr(), mean2.data_ptr(), invstd2.data_ptr(),
-                                         part2.data_ptr(), nblk2, 0)
+            s["bnr"] = _native.GemmBnBwdArgs(s["x2"].data_ptr(), s["mask2"].data_ptr(), mean2.data_ptr(),
+                                             invstd2.data_ptr(), part2.data_ptr(), nblk2, 0)
             sets.append(s)
 
         def two_kernels(s):
-            rc = bn.plx_bn_backward_from_partials(
-                s["x"].data_ptr(), s["mask"].data_ptr(), s["g"].data_ptr(), s["dy"].data_ptr(), None, m, k,
-                gamma.data_ptr(), mean.data_ptr(), invstd.data_ptr(), dgb.data_ptr(), dgb[k:].data_ptr(), coef.data_ptr(),
-                part.data_ptr(), nblk, l2.data_ptr(), 1, 0, None, cnt, st)
-            assert rc == 0
+            bn_backward(x=s["x"], mask=s["mask"], dy=s["g"], dx=s["dy"], m=m, c=k, gamma=gamma, save_mean=mean,
+                        save_invstd=invstd, dgamma=dgb, dbeta=dgb[k:], coef=coef, ext_part=part, ext_nblk=nblk,
+                        workspace=l2, relu=True, accumulate=0, counters=cnt, stream=st)
             rc = conv.plx_gemm_nt(s["dy"].data_ptr(), wt.data_ptr(), s["c"].data_ptr(), m, n, k, k, k, n, zero, None, None,
                                   0, None, ctypes.addressof(s["bnr"]), st)
             assert rc == 0
 
         def fused(s):
-            rc = bn.plx_bn_backward_coef_from_partials(
-                m, k, gamma.data_ptr(), mean.data_ptr(), invstd.data_ptr(), dgb.data_ptr(), dgb[k:].data_ptr(),
-                coef.data_ptr(), part.data_ptr(), nblk, l2.data_ptr(), 0, cnt, st)
-            assert rc == 0
+            bn_backward(x=s["x"], mask=s["mask"], dy=s["g"], dx=None, m=m, c=k, gamma=gamma, save_mean=mean,
+                        save_invstd=invstd, dgamma=dgb, dbeta=dgb[k:], coef=coef, ext_part=part, ext_nblk=nblk,
+                        workspace=l2, relu=True, accumulate=0, counters=cnt, stream=st)
             rc = conv.plx_gemm_nt_bndx(s["g"].data_ptr(), s["x"].data_ptr(), s["mask"].data_ptr(), coef.data_ptr(),
                                        s["dy"].data_ptr(), wt.data_ptr(), s["c"].data_ptr(), m, n, k, k, n, None, 0, None,
                                        ctypes.addressof(s["bnr"]), st)

@@ -4,7 +4,7 @@ alone, alternating off / on in one process through plx_bn_set_thin, one JSON lin
   stem_fwd    plx_stem_bn_pool_forward from given channel sums: finalize (a few us) + the apply/pool kernel
   stem_bwd    plx_stem_bn_pool_backward: partials pass + finalize + dx pass (a kernel trace of this script splits
               the two passes: `rocprofv3 --kernel-trace --stats -- python scripts/bn_thin_micro.py 5 2`)
-  res_dx_L    plx_bn_backward_from_partials with a ResBn (ReLU on, residual BatchNorm without ReLU, as the first
+  res_dx_L    plx_bn_backward from given partials with a ResBn (ReLU on, residual BatchNorm without ReLU, as the first
               block of each ResNet-50 stage runs it): finalize + the dx pass that also reduces the residual's partials.
               Not in the default list: that pass's thinned kernel missed the bar (profiles/bn_thin.md) and was
               removed, so both settings run the same kernel today; the cases are kept for a later attempt.
@@ -15,7 +15,6 @@ shapes.  The bar: the gain (difference of the medians) must exceed the old kerne
 
     python scripts/bn_thin_micro.py [reps] [warmup] [case ...]
 """
-import ctypes
 import json
 import os
 import statistics
@@ -26,7 +25,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from polyaxon_amd.ops import _native  # noqa: E402
-from polyaxon_amd.ops.bn_fused import _counters  # noqa: E402
+from polyaxon_amd.ops.bn_fused import _counters, bn_backward  # noqa: E402
 
 STEM = (256, 112, 112, 64)
 RES = {"res_dx_1": (802816, 256), "res_dx_2": (200704, 512), "res_dx_3": (50176, 1024), "res_dx_4": (12544, 2048)}
@@ -103,12 +102,9 @@ def res_case(lib, dev, st, m, c):
         sets.append(s)
 
     def run(s):
-        rc = lib.plx_bn_backward_from_partials(s["x"].data_ptr(), s["mask"].data_ptr(), s["dy"].data_ptr(),
-                                               s["dx"].data_ptr(), s["dres"].data_ptr(), m, c, gamma.data_ptr(),
-                                               mean.data_ptr(), invstd.data_ptr(), dgb.data_ptr(), dgb[c:].data_ptr(),
-                                               coef.data_ptr(), part_in.data_ptr(), 1, l2.data_ptr(), 1, 0,
-                                               ctypes.addressof(s["rb"]), cnt, st)
-        assert rc == 0
+        bn_backward(x=s["x"], mask=s["mask"], dy=s["dy"], dx=s["dx"], dres=s["dres"], m=m, c=c, gamma=gamma,
+                    save_mean=mean, save_invstd=invstd, dgamma=dgb, dbeta=dgb[c:], coef=coef, ext_part=part_in,
+                    ext_nblk=1, workspace=l2, relu=True, accumulate=0, resbn=s["rb"], counters=cnt, stream=st)
 
     return run, sets, nbytes
 

@@ -49,7 +49,8 @@ def main() -> None:
         mean = torch.zeros(n, dtype=torch.float32, device=dev)
         inv = torch.ones(n, dtype=torch.float32, device=dev)
         part = torch.empty(2 * nblk * n, dtype=torch.float32, device=dev)
-        bnr = _native.BnBwdArgs(x.data_ptr(), mask.data_ptr(), mean.data_ptr(), inv.data_ptr(), part.data_ptr(), nblk, 0)
+        bnr = _native.GemmBnBwdArgs(x.data_ptr(), mask.data_ptr(), mean.data_ptr(), inv.data_ptr(), part.data_ptr(),
+                                    nblk, 0)
 
         def run(stats_on=False, add=False, bn=False):
             return lambda: conv.plx_gemm_nt(a.data_ptr(), b.data_ptr(), c.data_ptr(), m, n, k, k, k, n, zero,

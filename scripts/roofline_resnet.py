@@ -37,6 +37,7 @@ def main() -> None:
     import torch
 
     from polyaxon_amd.ops import _native
+    from polyaxon_amd.ops.bn_fused import bn_backward, bn_forward
     from polyaxon_amd.ops.conv1x1 import _num_cus, _zero_page, nt_stats_rows
 
     dev = torch.device("cuda")
@@ -138,8 +139,8 @@ def main() -> None:
             bx, mask, mean, invstd = bn_args(m_in, cin)
             nblk = (-(-m_in // nt_stats_rows(cin))) if gemm else int(conv.plx_conv_dgrad_blocks(nb, h, w, cin, cout, k, s))
             part = torch.empty(2 * nblk * cin, **f32)
-            bnr = _native.BnBwdArgs(bx.data_ptr(), mask.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
-                                    part.data_ptr(), nblk, 0)
+            bnr = _native.GemmBnBwdArgs(bx.data_ptr(), mask.data_ptr(), mean.data_ptr(), invstd.data_ptr(),
+                                        part.data_ptr(), nblk, 0)
             extra += 2.0 * m_in * cin + m_in * cin / 8 + part.numel() * 4
         bp = ctypes.addressof(bnr) if bnr is not None else None
         if gemm:
@@ -177,11 +178,10 @@ def main() -> None:
         part = torch.rand(2 * nblk * c, **f32)
         l2 = torch.empty(int(bn.plx_bn_l2_workspace(nblk, c)), **f32)
         mo = torch.empty(m * c // 8, dtype=torch.uint8, device=dev) if relu else None
-        fwd = lambda: bn.plx_bn_forward_from_partials(  # noqa
-            x.data_ptr(), r.data_ptr() if r is not None else None, y.data_ptr(), m, c, weight.data_ptr(),
-            bias.data_ptr(), 1e-5, 0.1, rm.data_ptr(), rv.data_ptr(), stats.data_ptr(), stats[c:].data_ptr(),
-            stats[2 * c:].data_ptr(), part.data_ptr(), nblk, l2.data_ptr(),
-            mo.data_ptr() if mo is not None else None, int(relu), None, cptr, st)
+        fwd = lambda: bn_forward(  # noqa
+            x=x, res=r, y=y, m=m, c=c, gamma=weight, beta=bias, eps=1e-5, momentum=0.1, running_mean=rm,
+            running_var=rv, save_mean=stats, save_invstd=stats[c:], scale_bias=stats[2 * c:], ext_part=part,
+            ext_nblk=nblk, workspace=l2, mask=mo, relu=relu, counters=cptr, stream=st)
         nbytes = 2.0 * m * c * (2 + (1 if res else 0)) + (m * c / 8 if relu else 0)
         emit(name, "bn_fwd", count, timeit(fwd), nbytes, 0.0)
         if a.bn_apply_only:
@@ -192,18 +192,12 @@ def main() -> None:
         dx = torch.empty(m, c, **bf)
         dres = torch.empty(m, c, **bf) if res else None
         dg, db, coef = torch.zeros(c, **f32), torch.zeros(c, **f32), torch.empty(3 * c, **f32)
-        mp = mask.data_ptr() if relu else None
-        if partials_bwd:
-            bwd = lambda: bn.plx_bn_backward_from_partials(  # noqa
-                x.data_ptr(), mp, dy.data_ptr(), dx.data_ptr(), dres.data_ptr() if dres is not None else None, m, c,
-                weight.data_ptr(), mean.data_ptr(), invstd.data_ptr(), dg.data_ptr(), db.data_ptr(), coef.data_ptr(),
-                part.data_ptr(), nblk, l2.data_ptr(), int(relu), 1, None, cptr, st)
-        else:
-            pw = torch.empty(int(bn.plx_bn_workspace(m, c)), **f32)
-            bwd = lambda: bn.plx_bn_backward(  # noqa
-                x.data_ptr(), mp, dy.data_ptr(), dx.data_ptr(), dres.data_ptr() if dres is not None else None, m, c,
-                weight.data_ptr(), mean.data_ptr(), invstd.data_ptr(), dg.data_ptr(), db.data_ptr(), coef.data_ptr(),
-                pw.data_ptr(), int(relu), 1, None, cptr, st)
+        ext = dict(ext_part=part, ext_nblk=nblk, workspace=l2) if partials_bwd else dict(
+            workspace=torch.empty(int(bn.plx_bn_workspace(m, c)), **f32))
+        bwd = lambda: bn_backward(  # noqa
+            x=x, mask=mask if relu else None, dy=dy, dx=dx, dres=dres, m=m, c=c, gamma=weight, save_mean=mean,
+            save_invstd=invstd, dgamma=dg, dbeta=db, coef=coef, relu=relu, accumulate=1, counters=cptr, stream=st,
+            **ext)
         nbytes = 2.0 * m * c * (3 + (1 if res else 0)) + (m * c / 8 if relu else 0)
         emit(name, "bn_bwd" + ("" if partials_bwd else "+reduce"), count, timeit(bwd), nbytes, 0.0)
 
@@ -228,9 +222,9 @@ def main() -> None:
             ws.data_ptr(), None, 0, cptr, st)
 
         def fu():
-            bn.plx_bn_forward(x.data_ptr(), None, y.data_ptr(), m, c, weight.data_ptr(), bias.data_ptr(), 1e-5, 0.1,
-                              rm.data_ptr(), rv.data_ptr(), stats.data_ptr(), stats[c:].data_ptr(),
-                              stats[2 * c:].data_ptr(), ws.data_ptr(), mask.data_ptr(), 1, None, cptr, st)
+            bn_forward(x=x, y=y, m=m, c=c, gamma=weight, beta=bias, eps=1e-5, momentum=0.1, running_mean=rm,
+                       running_var=rv, save_mean=stats, save_invstd=stats[c:], scale_bias=stats[2 * c:], workspace=ws,
+                       mask=mask, relu=True, counters=cptr, stream=st)
             pool.plx_maxpool3s2_forward(y.data_ptr(), p.data_ptr(), idx.data_ptr(), n, h, w, c, st)
         nbytes = 2.0 * m * c * 2 + 3.0 * n * 56 * 56 * c
         emit(name + " fused", "fwd", 1, timeit(ff), nbytes, 0.0)
@@ -247,9 +241,8 @@ def main() -> None:
 
         def bu():
             pool.plx_maxpool3s2_backward(dp.data_ptr(), idx.data_ptr(), dy1.data_ptr(), n, h, w, c, st)
-            bn.plx_bn_backward(x.data_ptr(), mask.data_ptr(), dy1.data_ptr(), dx.data_ptr(), None, m, c,
-                               weight.data_ptr(), mean.data_ptr(), invstd.data_ptr(), dg.data_ptr(), db.data_ptr(),
-                               coef.data_ptr(), ws.data_ptr(), 1, 1, None, cptr, st)
+            bn_backward(x=x, mask=mask, dy=dy1, dx=dx, m=m, c=c, gamma=weight, save_mean=mean, save_invstd=invstd,
+                        dgamma=dg, dbeta=db, coef=coef, workspace=ws, relu=True, accumulate=1, counters=cptr, stream=st)
         nbytes = 2.0 * m * c * 2 + 3.0 * n * 56 * 56 * c
         emit(name + " fused", "bwd", 1, timeit(bf_), nbytes, 0.0)
         emit(name + " unfused", "bwd", 1, timeit(bu), nbytes, 0.0)

@@ -94,6 +94,7 @@ def test_reduce_finalize_one_launch_matches_two(cuda):
     backward coefficients to the two-launch path, over many row splits (S = 16) and repeated calls (the counters
     return to zero)."""
     from polyaxon_amd.ops import _native
+    from polyaxon_amd.ops.bn_fused import bn_backward, bn_forward
 
     lib = _native.lib("plx_bn")
     torch.manual_seed(7)
@@ -108,11 +109,9 @@ def test_reduce_finalize_one_launch_matches_two(cuda):
 
     def fwd(counters):
         stats, rm, rv = torch.empty(4 * c, **f32), torch.zeros(c, **f32), torch.ones(c, **f32)
-        rc = lib.plx_bn_forward_from_partials(x.data_ptr(), None, None, m, c, w.data_ptr(), b.data_ptr(), 1e-5, 0.1,
-                                              rm.data_ptr(), rv.data_ptr(), stats.data_ptr(), stats[c:].data_ptr(),
-                                              stats[2 * c:].data_ptr(), part.data_ptr(), nblk, l2.data_ptr(), None, 0,
-                                              None, counters, st)
-        assert rc == 0
+        bn_forward(x=x, m=m, c=c, gamma=w, beta=b, eps=1e-5, momentum=0.1, running_mean=rm, running_var=rv,
+                   save_mean=stats, save_invstd=stats[c:], scale_bias=stats[2 * c:], ext_part=part, ext_nblk=nblk,
+                   workspace=l2, counters=counters, stream=st)
         return torch.cat([stats, rm, rv])
 
     mean, inv = torch.randn(c, **f32), torch.rand(c, **f32) + 0.5
@@ -120,11 +119,8 @@ def test_reduce_finalize_one_launch_matches_two(cuda):
     def bwd(counters):
         dg, db, coef = torch.zeros(c, **f32), torch.zeros(c, **f32), torch.empty(3 * c, **f32)
         dx = torch.empty_like(x)
-        rc = lib.plx_bn_backward_from_partials(x.data_ptr(), None, x.data_ptr(), dx.data_ptr(), None, m, c,
-                                               w.data_ptr(), mean.data_ptr(), inv.data_ptr(), dg.data_ptr(),
-                                               db.data_ptr(), coef.data_ptr(), part.data_ptr(), nblk, l2.data_ptr(),
-                                               0, 1, None, counters, st)
-        assert rc == 0
+        bn_backward(x=x, dy=x, dx=dx, m=m, c=c, gamma=w, save_mean=mean, save_invstd=inv, dgamma=dg, dbeta=db,
+                    coef=coef, ext_part=part, ext_nblk=nblk, workspace=l2, accumulate=1, counters=counters, stream=st)
         return torch.cat([dg, db, coef])
 
     ref_f, ref_b = fwd(None), bwd(None)
@@ -145,6 +141,7 @@ def test_fence_free_handoff_stress(cuda):
     second stream keeps every CU busy with a streaming copy (uneven load, consumers L1-warm from the previous call):
     every result bitwise equals the two-launch path (whose hand-off is a kernel boundary)."""
     from polyaxon_amd.ops import _native
+    from polyaxon_amd.ops.bn_fused import bn_forward
 
     lib = _native.lib("plx_bn")
     torch.manual_seed(11)
@@ -161,11 +158,9 @@ def test_fence_free_handoff_stress(cuda):
 
     def fwd(part, counters):
         stats, rm, rv = torch.empty(4 * c, **f32), torch.zeros(c, **f32), torch.ones(c, **f32)
-        rc = lib.plx_bn_forward_from_partials(x.data_ptr(), None, None, m, c, w.data_ptr(), b.data_ptr(), 1e-5, 0.1,
-                                              rm.data_ptr(), rv.data_ptr(), stats.data_ptr(), stats[c:].data_ptr(),
-                                              stats[2 * c:].data_ptr(), part.data_ptr(), nblk, l2.data_ptr(), None, 0,
-                                              None, counters, torch.cuda.current_stream().cuda_stream)
-        assert rc == 0
+        bn_forward(x=x, m=m, c=c, gamma=w, beta=b, eps=1e-5, momentum=0.1, running_mean=rm, running_var=rv,
+                   save_mean=stats, save_invstd=stats[c:], scale_bias=stats[2 * c:], ext_part=part, ext_nblk=nblk,
+                   workspace=l2, counters=counters, stream=torch.cuda.current_stream().cuda_stream)
         return torch.cat([stats, rm, rv])
 
     refs = [fwd(p, None) for p in parts]
@@ -228,3 +223,120 @@ def test_stem_bn_relu_pool_matches_unfused(cuda, shape):
     torch.testing.assert_close(yf, yr, rtol=2e-2, atol=2e-2)
     torch.testing.assert_close(dgf, wr.grad, rtol=5e-2, atol=5e-2 * float(wr.grad.abs().max()))
     torch.testing.assert_close(dbf, br.grad, rtol=5e-2, atol=5e-2 * float(br.grad.abs().max()))
+
+
+def test_bn_args_layout_matches_library(cuda):
+    """The ctypes images of plx_bn_forward / plx_bn_backward's argument structs have the library's sizes."""
+    import ctypes
+
+    from polyaxon_amd.ops import _native
+
+    lib = _native.lib("plx_bn")
+    assert lib.plx_bn_args_size(0) == ctypes.sizeof(_native.BnForwardArgs)
+    assert lib.plx_bn_args_size(1) == ctypes.sizeof(_native.BnBackwardArgs)
+
+
+def test_bn_refused_calls_launch_nothing(cuda):
+    """Every argument combination the entry points refuse returns non-zero (the helpers raise) before any launch:
+    afterwards every output buffer still holds its sentinel."""
+    from polyaxon_amd.ops import _native
+    from polyaxon_amd.ops.bn_fused import bn_backward, bn_forward
+
+    lib = _native.lib("plx_bn")
+    torch.manual_seed(3)
+    n, c, h, w = 2, 64, 3, 3
+    m, nblk = n * h * w, 3
+    sentinel = {torch.bfloat16: -7.0, torch.float32: -12345.0, torch.uint8: 0xA5, torch.int32: 77}
+    outs = {}
+
+    def out(name, numel, dtype=torch.float32):
+        outs[name] = torch.full((numel,), sentinel[dtype], dtype=dtype, device=cuda)
+        return outs[name]
+
+    f32 = dict(dtype=torch.float32, device=cuda)
+    x = torch.randn(m, c, device=cuda).to(torch.bfloat16)
+    dy, x2 = torch.randn_like(x), torch.randn_like(x)
+    gamma, beta = torch.rand(c, **f32) + 0.5, torch.randn(c, **f32)
+    mean, inv = torch.randn(c, **f32), torch.rand(c, **f32) + 0.5
+    part = torch.rand(2 * nblk * c, **f32) * 4.0
+    in_mask = torch.randint(0, 256, (m * c // 8,), device=cuda, dtype=torch.int32).to(torch.uint8)
+    ws = out("workspace", int(lib.plx_bn_workspace(m, c)))
+    stats = out("stats", 4 * c)
+    fwd = dict(x=x, y=out("y", m * c, torch.bfloat16), m=m, c=c, gamma=gamma, beta=beta, eps=1e-5, momentum=0.1,
+               running_mean=out("running_mean", c), running_var=out("running_var", c), save_mean=stats,
+               save_invstd=stats[c:], scale_bias=stats[2 * c:], workspace=ws, mask=out("mask", m * c // 8, torch.uint8),
+               relu=True, counters=out("counters", 64, torch.int32))
+    bwd = dict(x=x, mask=in_mask, dy=dy, dx=out("dx", m * c, torch.bfloat16), m=m, c=c, gamma=gamma, save_mean=mean,
+               save_invstd=inv, dgamma=out("dgamma", c), dbeta=out("dbeta", c), coef=out("coef", 3 * c), workspace=ws,
+               relu=True, counters=outs["counters"])
+    dres = out("dres", m * c, torch.bfloat16)
+    rpart = out("resbn_part", 2 * int(lib.plx_bn_dx_blocks(m, c)) * c)
+    resbn = _native.ResBnArgs(x2.data_ptr(), None, mean.data_ptr(), inv.data_ptr(), rpart.data_ptr())
+    resbn_no_part = _native.ResBnArgs(x2.data_ptr(), None, mean.data_ptr(), inv.data_ptr(), None)
+    ext = dict(ext_part=part, ext_nblk=nblk)
+    refused = [
+        (bn_forward, dict(fwd, c=24)),                                   # plan_for fails
+        (bn_forward, dict(fwd, m=0)),
+        (bn_forward, dict(fwd, ext_part=part, ext_nblk=0)),
+        (bn_backward, dict(bwd, c=24)),
+        (bn_backward, dict(bwd, m=0)),
+        (bn_backward, dict(bwd, ext_part=part, ext_nblk=0)),
+        (bn_backward, dict(bwd, mask=None)),                             # the reduce and the dx pass read the mask
+        (bn_backward, dict(bwd, mask=None, dx=None)),                    # the reduce pass does
+        (bn_backward, dict(bwd, mask=None, **ext)),                      # the dx pass does
+        (bn_backward, dict(bwd, resbn=resbn)),                           # a ResBn without dres
+        (bn_backward, dict(bwd, resbn=resbn_no_part, dres=dres)),        # ... without part
+        (bn_backward, dict(bwd, dx=None, dres=dres)),                    # no dx pass, but something for it to write
+        (bn_backward, dict(bwd, dx=None, dres=dres, resbn=resbn)),
+        (bn_backward, dict(bwd, dx=None, resbn=resbn, **ext)),
+    ]
+    for fn, kw in refused:
+        with pytest.raises(RuntimeError, match="failed with code"):
+            fn(**kw)
+    torch.cuda.synchronize()
+    for name, t in outs.items():
+        assert bool((t == sentinel[t.dtype]).all()), f"{name} was written by a refused call"
+
+
+@pytest.mark.parametrize("counters", [False, True], ids=["two_launch", "one_launch"])
+@pytest.mark.parametrize("accumulate", [0, 1], ids=["fresh", "accumulate"])
+@pytest.mark.parametrize("external", [False, True], ids=["own_reduce", "ext_partials"])
+@pytest.mark.parametrize("shape,relu", [((2, 256, 7, 9), True), ((2, 128, 1, 1), False)],
+                         ids=["256x7x9_relu", "128x1x1"])
+def test_bn_backward_coef_only_equals_full(cuda, shape, relu, external, accumulate, counters):
+    """plx_bn_backward with dx = None (reduce + finalize only) gives dgamma, dbeta and coef bit for bit as the call
+    that also writes dx: both run the same reduction in the same fixed order, so no tolerance is involved."""
+    from polyaxon_amd.ops import _native
+    from polyaxon_amd.ops.bn_fused import bn_backward
+
+    lib = _native.lib("plx_bn")
+    torch.manual_seed(5)
+    n, c, h, w = shape
+    m, nblk = n * h * w, 3
+    f32 = dict(dtype=torch.float32, device=cuda)
+    x = torch.randn(m, c, device=cuda).to(torch.bfloat16)
+    dy = torch.randn_like(x)
+    mask = torch.randint(0, 256, (m * c // 8,), device=cuda, dtype=torch.int32).to(torch.uint8) if relu else None
+    gamma, mean, inv = torch.rand(c, **f32) + 0.5, torch.randn(c, **f32), torch.rand(c, **f32) + 0.5
+    dgb0 = torch.randn(2 * c, **f32)
+    cnt = torch.zeros(64, dtype=torch.int32, device=cuda) if counters else None
+    if external:
+        ext = dict(ext_part=torch.rand(2 * nblk * c, **f32) * 4.0, ext_nblk=nblk)
+        nws = int(lib.plx_bn_l2_workspace(nblk, c))
+    else:
+        ext, nws = {}, int(lib.plx_bn_workspace(m, c))
+
+    def run(dx):
+        dgb, coef = dgb0.clone(), torch.empty(3 * c, **f32)
+        bn_backward(x=x, mask=mask, dy=dy, dx=dx, m=m, c=c, gamma=gamma, save_mean=mean, save_invstd=inv, dgamma=dgb,
+                    dbeta=dgb[c:], coef=coef, workspace=torch.empty(nws, **f32), relu=relu, accumulate=accumulate,
+                    counters=cnt, **ext)
+        return dgb, coef
+
+    full, coef_only = run(torch.empty_like(x)), run(None)
+    torch.cuda.synchronize()
+    for a, b in zip(coef_only, full):
+        assert bool(torch.isfinite(b).all())
+        assert torch.equal(a, b)
+    if cnt is not None:
+        assert int(cnt.abs().sum()) == 0

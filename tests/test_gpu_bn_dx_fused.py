@@ -32,7 +32,7 @@ def _case(m: int, k: int, n: int, relu: bool):
     """Inputs of one case, the standalone BatchNorm backward (its dx and the coefficients of its real finalize) and
     the fp32 autograd reference, computed once and shared (read-only) by the tests of that case."""
     from polyaxon_amd.ops import _native
-    from polyaxon_amd.ops.bn_fused import _counters, _stream
+    from polyaxon_amd.ops.bn_fused import _counters, _stream, bn_backward, bn_forward
 
     dev = torch.device("cuda", 0)
     gen = torch.Generator(device=dev).manual_seed(1000 * m + k + n + int(relu))
@@ -46,23 +46,18 @@ def _case(m: int, k: int, n: int, relu: bool):
     d_add = rnd(m, n).to(torch.bfloat16)                      # a second gradient added in the epilogue
 
     # --- native BatchNorm forward (mask, mean, invstd) and standalone backward (dx, coef)
-    lib = _native.lib("plx_bn")
     f32 = dict(dtype=torch.float32, device=dev)
     ws = _native.size("plx_bn", "plx_bn_workspace", m, k)
     stats = torch.empty(4 * k, **f32)
     y = torch.empty_like(x)
     mask = torch.empty(m * k // 8, dtype=torch.uint8, device=dev) if relu else None
-    mp = mask.data_ptr() if relu else None
-    rc = lib.plx_bn_forward(x.data_ptr(), None, y.data_ptr(), m, k, gamma.data_ptr(), beta.data_ptr(), EPS, 0.1, None,
-                            None, stats.data_ptr(), stats[k:].data_ptr(), stats[2 * k:].data_ptr(),
-                            torch.empty(ws, **f32).data_ptr(), mp, int(relu), None, _counters(dev), _stream())
-    assert rc == 0
+    bn_forward(x=x, y=y, m=m, c=k, gamma=gamma, beta=beta, eps=EPS, momentum=0.1, save_mean=stats,
+               save_invstd=stats[k:], scale_bias=stats[2 * k:], workspace=torch.empty(ws, **f32), mask=mask, relu=relu,
+               counters=_counters(dev), stream=_stream())
     dx, coef, dgb = torch.empty_like(x), torch.empty(3 * k, **f32), torch.empty(2 * k, **f32)
-    rc = lib.plx_bn_backward(x.data_ptr(), mp, g.data_ptr(), dx.data_ptr(), None, m, k, gamma.data_ptr(),
-                             stats.data_ptr(), stats[k:].data_ptr(), dgb.data_ptr(), dgb[k:].data_ptr(),
-                             coef.data_ptr(), torch.empty(ws, **f32).data_ptr(), int(relu), 0, None, _counters(dev),
-                             _stream())
-    assert rc == 0
+    bn_backward(x=x, mask=mask, dy=g, dx=dx, m=m, c=k, gamma=gamma, save_mean=stats, save_invstd=stats[k:],
+                dgamma=dgb, dbeta=dgb[k:], coef=coef, workspace=torch.empty(ws, **f32), relu=relu, accumulate=0,
+                counters=_counters(dev), stream=_stream())
 
     # --- fp32 reference: dy = d sum(g * act(BN(x))) / dx, C = conv2d's data gradient of dy, and the gradients of the
     # previous BatchNorm's gamma / beta for the output gradient C (+ d_add) = the column sums of the partials
@@ -104,8 +99,8 @@ def _run(case, m, k, n, fused: bool, epilogue: bool):
     if epilogue:
         nblk = -(-m // nt_stats_rows(n))
         part = torch.full((2, nblk, n), float("nan"), device=dev)
-        bnr = _native.BnBwdArgs(case["xp"].data_ptr(), case["mask_p"].data_ptr(), case["mean_p"].data_ptr(),
-                                case["invstd_p"].data_ptr(), part.data_ptr(), nblk, 0)
+        bnr = _native.GemmBnBwdArgs(case["xp"].data_ptr(), case["mask_p"].data_ptr(), case["mean_p"].data_ptr(),
+                                    case["invstd_p"].data_ptr(), part.data_ptr(), nblk, 0)
         add = case["d_add"]
     if fused:
         gemm_nt_bndx(case["g"], case["x"], case["mask"], case["coef"], dy, case["wt"], out, add=add, bnr=bnr)

@@ -21,8 +21,6 @@ Loop coverage of the new kernels:
   later attempt: (4200, 2048) has 1,075,200 vectors on 4096 x 256 threads (a second, ragged grid-stride trip), (37, 64)
   and (1000, 256) leave the last block partly idle.
 """
-import ctypes
-
 import pytest
 import torch
 
@@ -192,6 +190,7 @@ def _res_inputs(m, c, dev):
 
 def _res_backward(lib, thin, m, c, t, relu, rmask):
     from polyaxon_amd.ops import _native
+    from polyaxon_amd.ops.bn_fused import bn_backward
 
     dev = t["x"].device
     lib.plx_bn_set_thin(thin)
@@ -206,21 +205,17 @@ def _res_backward(lib, thin, m, c, t, relu, rmask):
     ws = torch.empty(int(lib.plx_bn_workspace(m, c)), **f32)
     rb = _native.ResBnArgs(t["x2"].data_ptr(), t["mask2"].data_ptr() if rmask else None, t["mean2"].data_ptr(),
                            t["invstd2"].data_ptr(), part.ptr)
-    rc = lib.plx_bn_backward(t["x"].data_ptr(), t["mask"].data_ptr() if relu else None, t["dy"].data_ptr(), dx.ptr,
-                             dres.ptr, m, c, t["gamma"].data_ptr(), t["mean"].data_ptr(), t["invstd"].data_ptr(),
-                             dgb.data_ptr(), dgb[c:].data_ptr(), coef.data_ptr(), ws.data_ptr(), int(relu), 0,
-                             ctypes.addressof(rb), cnt, st)
-    assert rc == 0
+    bn_backward(x=t["x"], mask=t["mask"] if relu else None, dy=t["dy"], dx=dx.ptr, dres=dres.ptr, m=m, c=c,
+                gamma=t["gamma"], save_mean=t["mean"], save_invstd=t["invstd"], dgamma=dgb, dbeta=dgb[c:], coef=coef,
+                workspace=ws, relu=relu, accumulate=0, resbn=rb, counters=cnt, stream=st)
     # the residual BatchNorm's backward from those partials (no reduce pass of its own)
     dx2 = Guarded(m * c, torch.bfloat16, dev)
     dgb2 = Guarded(2 * c, torch.float32, dev)
     coef2 = torch.empty(3 * c, **f32)
     l2 = torch.empty(int(lib.plx_bn_l2_workspace(nblk2, c)), **f32)
-    rc = lib.plx_bn_backward_from_partials(t["x2"].data_ptr(), t["mask2"].data_ptr() if rmask else None, dres.ptr,
-                                           dx2.ptr, None, m, c, t["gamma2"].data_ptr(), t["mean2"].data_ptr(),
-                                           t["invstd2"].data_ptr(), dgb2.ptr, dgb2.t[c:].data_ptr(), coef2.data_ptr(),
-                                           part.ptr, nblk2, l2.data_ptr(), int(rmask), 0, None, cnt, st)
-    assert rc == 0
+    bn_backward(x=t["x2"], mask=t["mask2"] if rmask else None, dy=dres.ptr, dx=dx2.ptr, m=m, c=c, gamma=t["gamma2"],
+                save_mean=t["mean2"], save_invstd=t["invstd2"], dgamma=dgb2.ptr, dbeta=dgb2.t[c:], coef=coef2,
+                ext_part=part.ptr, ext_nblk=nblk2, workspace=l2, relu=rmask, accumulate=0, counters=cnt, stream=st)
     torch.cuda.synchronize()
     return dx.check(), dres.check(), part.check(), dgb2.check(), dx2.check()
 
