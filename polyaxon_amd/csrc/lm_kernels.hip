@@ -11,6 +11,15 @@
 //                      (online max / sum over 16-byte chunks, one workgroup per row) and loss = lse - x[target]
 //   plx_xent_bwd       dlogits[B][S][V] (bf16) = (softmax - onehot(target)) * dloss / rows, zero rows at s = S-1
 //   plx_xent_cls_*     the same pair for classification logits [N][V] and labels [N] (the ResNet head)
+//   plx_xent_hp_*      both pairs (plx_xent_hp_fwd / _bwd, plx_xent_cls_hp_fwd / _bwd) with the loss's per-trial
+//                      hyper-parameters read from device memory at run time -- lhp[0] = eps (label smoothing), lhp[1]
+//                      = zeta (z-loss), lhp[2..3] reserved -- and C real classes of the V columns (columns >= C are
+//                      vocabulary padding: in the softmax as they are, outside the smoothing term):
+//                        nll = lse - x[t],  loss = lse - (1-eps) x[t] - eps mean_{j<C} x[j] + zeta lse^2
+//                        grad[j] = (p[j] (1 + 2 zeta lse) - (1-eps)[j == t] - (eps/C)[j < C]) * dloss / rows
+//                      the same row walk with one more sum (of x[j], j < C) in the forward and one multiply-add per
+//                      element in the backward; a captured step serves every (eps, zeta), and at eps = zeta = 0,
+//                      C = V the factors are exactly 1.0 and 0.0: lse, loss and grad are bitwise the plain pair's
 //                      -- replaces slice copy + fp32 cast + log_softmax + NLL and their backward chain (~5.5 ms of
 //                      a 37 ms GPT-2 125M step: vocab 50257 x 16k tokens through fp32 twice)
 //   plx_colsum         bias gradients: out[N] = sum over rows of a bf16 [T][N] matrix, fp32 accumulation, one launch
@@ -204,10 +213,15 @@ __device__ __forceinline__ void lse_combine(float& m, float& s, float m2, float 
 
 // CLS: classification rows instead of next-token positions -- logits [N][V], target labels[r] of row r (the
 // ResNet head's cross entropy, ops/lm.py class_xent); S is unused then
-template <bool CLS = false>
+// HP: the loss's device hyper-parameters lhp = {eps, zeta, 0, 0} and C <= V real classes (ops/loss_hp.py): the walk
+// also sums x[j] over j < C, `loss` is the smoothed + z-loss training loss and `nll` the plain one; without HP
+// lhp / nll are unused and C == V
+template <bool CLS = false, bool HP = false>
 __global__ __launch_bounds__(kBlock) void xent_fwd_kernel(const uint16_t* __restrict__ logits,
                                                           const int64_t* __restrict__ tokens, float* __restrict__ lse,
-                                                          float* __restrict__ loss, int S, int V) {
+                                                          float* __restrict__ loss, int S, int V,
+                                                          const float* __restrict__ lhp, float* __restrict__ nll,
+                                                          int C) {
   const int r = blockIdx.x;                      // loss row: (b, s), s < S - 1
   const int b = CLS ? r : r / (S - 1), s = CLS ? 0 : r - b * (S - 1);
   const int64_t lrow = CLS ? (int64_t)r : (int64_t)b * S + s;
@@ -216,7 +230,7 @@ __global__ __launch_bounds__(kBlock) void xent_fwd_kernel(const uint16_t* __rest
   const bf16x8* base = (const bf16x8*)(p0 & ~(uintptr_t)15);
   const int head = (int)((p0 & 15) >> 1);
   const int nch = (head + V + 7) >> 3;
-  float m = kNegInf, sum = 0.f;
+  float m = kNegInf, sum = 0.f, sx = 0.f;  // sx (HP): this lane's sum of x[j], j < C
   // 4 chunks (64 bytes) per lane in flight per trip: one load per trip left the row walk latency-bound (~3.9 TB/s)
   for (int c0 = threadIdx.x; c0 < nch; c0 += 4 * kBlock) {
     bf16x8 v[4];
@@ -234,6 +248,17 @@ __global__ __launch_bounds__(kBlock) void xent_fwd_kernel(const uint16_t* __rest
         x[u][j] = (e >= 0 && e < V) ? bf2f(v[u].v[j]) : kNegInf;
         cm = fmaxf(cm, x[u][j]);
       }
+    if (HP) {  // one add per element, before the all -inf skip: the padding chunks add 0, not nothing
+      float cx = 0.f;
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const int e = (c0 + u * kBlock) * 8 + j - head;
+          cx += (e >= 0 && e < C) ? x[u][j] : 0.f;
+        }
+      sx += cx;
+    }
     if (cm == kNegInf) continue;
     float cs = 0.f;
 #pragma unroll
@@ -244,11 +269,16 @@ __global__ __launch_bounds__(kBlock) void xent_fwd_kernel(const uint16_t* __rest
   }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) lse_combine(m, sum, __shfl_xor(m, off), __shfl_xor(sum, off));
-  __shared__ float sm[kBlock / 64], ss[kBlock / 64];
+  if (HP) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) sx += __shfl_xor(sx, off);
+  }
+  __shared__ float sm[kBlock / 64], ss[kBlock / 64], sxs[kBlock / 64];
   const int wave = threadIdx.x >> 6;
   if ((threadIdx.x & 63) == 0) {
     sm[wave] = m;
     ss[wave] = sum;
+    if (HP) sxs[wave] = sx;
   }
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -256,17 +286,36 @@ __global__ __launch_bounds__(kBlock) void xent_fwd_kernel(const uint16_t* __rest
     const float l = m + __logf(sum);
     const int64_t t = CLS ? tokens[r] : tokens[lrow + 1];
     lse[r] = l;
-    // a label outside [0, V) (ignore_index -100, or a bad label) contributes nothing and is never read
-    loss[r] = (t >= 0 && t < V) ? l - bf2f(row[t]) : 0.f;
+    if (!HP) {
+      // a label outside [0, V) (ignore_index -100, or a bad label) contributes nothing and is never read
+      loss[r] = (t >= 0 && t < V) ? l - bf2f(row[t]) : 0.f;
+    } else {
+      for (int w = 1; w < kBlock / 64; ++w) sx += sxs[w];
+      const float eps = lhp[0], zeta = lhp[1];
+      float lo = 0.f, nl = 0.f;
+      if (t >= 0 && t < C) {  // a target in the padding [C, V) is ignored like one outside the row
+        const float xt = bf2f(row[t]);
+        nl = l - xt;
+        // eps = zeta = 0: (1 - 0) xt is xt, the smoothing term is 0.0 whatever the row holds (a row with a -inf real
+        // logit has a -inf mean: 0 x -inf would be NaN, hence the per-row select) and zeta l^2 is 0.0 -- bitwise nl
+        const float smooth = eps != 0.f ? eps * (sx / (float)C) : 0.f;
+        lo = (l - (1.f - eps) * xt) - smooth + zeta * l * l;
+      }
+      loss[r] = lo;
+      nll[r] = nl;
+    }
   }
 }
 
 // scale: device scalar dloss (the mean's incoming gradient); inv_rows = 1 / (B * (S - 1))
-template <bool CLS = false>
+// HP: lhp / C as in the forward -- the softmax is scaled by 1 + 2 zeta lse, the one-hot by 1 - eps, and eps / C is
+// taken from every real class; targets outside [0, C) give zero rows (C == V without HP)
+template <bool CLS = false, bool HP = false>
 __global__ __launch_bounds__(kBlock) void xent_bwd_kernel(const uint16_t* __restrict__ logits,
                                                           const int64_t* __restrict__ tokens,
                                                           const float* __restrict__ lse, const float* __restrict__ dloss,
-                                                          uint16_t* __restrict__ grad, int S, int V, float inv_rows) {
+                                                          uint16_t* __restrict__ grad, int S, int V, float inv_rows,
+                                                          const float* __restrict__ lhp, int C) {
   const int lrow = blockIdx.x;                   // every logits row (b, s), s < S
   const int b = CLS ? lrow : lrow / S, s = CLS ? 0 : lrow - b * S;
   uint16_t* grow = grad + (int64_t)lrow * V;
@@ -275,7 +324,7 @@ __global__ __launch_bounds__(kBlock) void xent_bwd_kernel(const uint16_t* __rest
   const int head = (int)((q0 & 15) >> 1);       // logits and grad share the layout (same offsets)
   const int nch = (head + V + 7) >> 3;
   const int64_t tl = CLS ? tokens[lrow] : (s < S - 1 ? tokens[(int64_t)lrow + 1] : 0);
-  if ((!CLS && s == S - 1) || tl < 0 || tl >= V) {  // predicts nothing (last position, ignored label): zero gradient
+  if ((!CLS && s == S - 1) || tl < 0 || tl >= C) {  // predicts nothing (last position, ignored label): zero gradient
     for (int c = threadIdx.x; c < nch; c += kBlock) {
       if (c * 8 - head >= 0 && c * 8 - head + 8 <= V) {
         gbase[c] = bf16x8{};
@@ -292,6 +341,9 @@ __global__ __launch_bounds__(kBlock) void xent_bwd_kernel(const uint16_t* __rest
   const int r = CLS ? lrow : b * (S - 1) + s;
   const float l = lse[r], g = dloss[0] * inv_rows;
   const int64_t t = tl;
+  // exactly 1.0, 1.0 and 0.0 at eps = zeta = 0: p * 1 - 1 - 0 rounds as p - 1 does (fused or not)
+  const float eps = HP ? lhp[0] : 0.f, zeta = HP ? lhp[1] : 0.f;
+  const float pscale = fmaf(2.f * zeta, l, 1.f), hot = 1.f - eps, smooth = eps / (float)C;
   const bf16x8* base = (const bf16x8*)((uintptr_t)(logits + (int64_t)lrow * V) & ~(uintptr_t)15);
   for (int c = threadIdx.x; c < nch; c += kBlock) {
     const bf16x8 v = base[c];
@@ -300,7 +352,10 @@ __global__ __launch_bounds__(kBlock) void xent_bwd_kernel(const uint16_t* __rest
     for (int j = 0; j < 8; ++j) {
       const int e = c * 8 + j - head;
       const float p = __expf(bf2f(v.v[j]) - l);
-      o.v[j] = f2bf((p - (e == t ? 1.f : 0.f)) * g);
+      if (HP)
+        o.v[j] = f2bf((p * pscale - (e == t ? hot : 0.f) - (e < C ? smooth : 0.f)) * g);
+      else
+        o.v[j] = f2bf((p - (e == t ? 1.f : 0.f)) * g);
     }
     if (c * 8 - head >= 0 && c * 8 - head + 8 <= V) {
       gbase[c] = o;
@@ -466,7 +521,7 @@ PLX_API int plx_xent_fwd(const void* logits, const int64_t* tokens, float* lse, 
                          hipStream_t stream) {
   if (B <= 0 || S < 2 || V <= 0) return 1;
   hipLaunchKernelGGL(xent_fwd_kernel<false>, dim3(B * (S - 1)), dim3(kBlock), 0, stream, (const uint16_t*)logits, tokens,
-                     lse, loss, S, V);
+                     lse, loss, S, V, nullptr, nullptr, V);
   return (int)hipGetLastError();
 }
 
@@ -475,7 +530,7 @@ PLX_API int plx_xent_cls_fwd(const void* logits, const int64_t* labels, float* l
                              hipStream_t stream) {
   if (N <= 0 || V <= 0) return 1;
   hipLaunchKernelGGL(xent_fwd_kernel<true>, dim3(N), dim3(kBlock), 0, stream, (const uint16_t*)logits, labels, lse, loss,
-                     1, V);
+                     1, V, nullptr, nullptr, V);
   return (int)hipGetLastError();
 }
 
@@ -485,7 +540,7 @@ PLX_API int plx_xent_cls_bwd(const void* logits, const int64_t* labels, const fl
                              void* grad, int N, int V, float scale, hipStream_t stream) {
   if (N <= 0 || V <= 0) return 1;
   hipLaunchKernelGGL(xent_bwd_kernel<true>, dim3(N), dim3(kBlock), 0, stream, (const uint16_t*)logits, labels, lse,
-                     dloss, (uint16_t*)grad, 1, V, scale > 0.f ? scale : 1.f / (float)N);
+                     dloss, (uint16_t*)grad, 1, V, scale > 0.f ? scale : 1.f / (float)N, nullptr, V);
   return (int)hipGetLastError();
 }
 
@@ -494,7 +549,44 @@ PLX_API int plx_xent_bwd(const void* logits, const int64_t* tokens, const float*
                          int B, int S, int V, hipStream_t stream) {
   if (B <= 0 || S < 2 || V <= 0) return 1;
   hipLaunchKernelGGL(xent_bwd_kernel<false>, dim3(B * S), dim3(kBlock), 0, stream, (const uint16_t*)logits, tokens,
-                     lse, dloss, (uint16_t*)grad, S, V, 1.f / (float)(B * (S - 1)));
+                     lse, dloss, (uint16_t*)grad, S, V, 1.f / (float)(B * (S - 1)), nullptr, V);
+  return (int)hipGetLastError();
+}
+
+// The two pairs with device-resident loss hyper-parameters: lhp fp32 [4] = {eps (label smoothing), zeta (z-loss), 0,
+// 0}, read by the kernels at run time; C real classes (1 <= C <= V; columns >= C are padding); nll fp32 [rows]: the
+// plain negative log-likelihood next to the training loss.  A target outside [0, C) is ignored.
+PLX_API int plx_xent_hp_fwd(const void* logits, const int64_t* tokens, const float* lhp, float* lse, float* loss,
+                            float* nll, int B, int S, int V, int C, hipStream_t stream) {
+  if (B <= 0 || S < 2 || V <= 0 || C < 1 || C > V) return 1;
+  hipLaunchKernelGGL((xent_fwd_kernel<false, true>), dim3(B * (S - 1)), dim3(kBlock), 0, stream,
+                     (const uint16_t*)logits, tokens, lse, loss, S, V, lhp, nll, C);
+  return (int)hipGetLastError();
+}
+
+PLX_API int plx_xent_hp_bwd(const void* logits, const int64_t* tokens, const float* lse, const float* lhp,
+                            const float* dloss, void* grad, int B, int S, int V, int C, hipStream_t stream) {
+  if (B <= 0 || S < 2 || V <= 0 || C < 1 || C > V) return 1;
+  hipLaunchKernelGGL((xent_bwd_kernel<false, true>), dim3(B * S), dim3(kBlock), 0, stream, (const uint16_t*)logits,
+                     tokens, lse, dloss, (uint16_t*)grad, S, V, 1.f / (float)(B * (S - 1)), lhp, C);
+  return (int)hipGetLastError();
+}
+
+PLX_API int plx_xent_cls_hp_fwd(const void* logits, const int64_t* labels, const float* lhp, float* lse, float* loss,
+                                float* nll, int N, int V, int C, hipStream_t stream) {
+  if (N <= 0 || V <= 0 || C < 1 || C > V) return 1;
+  hipLaunchKernelGGL((xent_fwd_kernel<true, true>), dim3(N), dim3(kBlock), 0, stream, (const uint16_t*)logits, labels,
+                     lse, loss, 1, V, lhp, nll, C);
+  return (int)hipGetLastError();
+}
+
+// scale as in plx_xent_cls_bwd (<= 0: 1 / N)
+PLX_API int plx_xent_cls_hp_bwd(const void* logits, const int64_t* labels, const float* lse, const float* lhp,
+                                const float* dloss, void* grad, int N, int V, int C, float scale,
+                                hipStream_t stream) {
+  if (N <= 0 || V <= 0 || C < 1 || C > V) return 1;
+  hipLaunchKernelGGL((xent_bwd_kernel<true, true>), dim3(N), dim3(kBlock), 0, stream, (const uint16_t*)logits, labels,
+                     lse, dloss, (uint16_t*)grad, 1, V, scale > 0.f ? scale : 1.f / (float)N, lhp, C);
   return (int)hipGetLastError();
 }
 

@@ -261,7 +261,9 @@ class Transformer(nn.Module):
         return sum(p.numel() for p in self.parameters())
 
 
-def lm_loss(logits: torch.Tensor, tokens: torch.Tensor) -> torch.Tensor:
+def lm_loss(logits: torch.Tensor, tokens: torch.Tensor, loss_hp=None, n_classes: Optional[int] = None) -> torch.Tensor:
     """Next-token cross entropy (targets = tokens shifted left), mean over B * (S - 1) positions: the fused HIP kernels
-    on bf16 GPU logits (ops/lm.py next_token_xent), F.cross_entropy in fp32 otherwise."""
-    return lm_ops.next_token_xent(logits, tokens)
+    on bf16 GPU logits (ops/lm.py next_token_xent), F.cross_entropy in fp32 otherwise.  ``loss_hp`` / ``n_classes``:
+    label smoothing and z-loss as device data over the ``n_classes`` real columns of a padded vocabulary
+    (``cfg.vocab_size`` of ``cfg.vocab_rows``)."""
+    return lm_ops.next_token_xent(logits, tokens, loss_hp=loss_hp, n_classes=n_classes)

@@ -172,12 +172,80 @@ class _NextTokenXent(torch.autograd.Function):
         return grad, None
 
 
-def next_token_xent(logits: torch.Tensor, tokens: torch.Tensor) -> torch.Tensor:
+def _classes(n_classes: Optional[int], V: int) -> int:
+    C = V if n_classes is None else int(n_classes)
+    if not 1 <= C <= V:
+        raise ValueError(f"n_classes must be in [1, {V}], got {n_classes!r}")
+    return C
+
+
+def _xent_hp_reference(x: torch.Tensor, y: torch.Tensor, loss_hp, C: int, rows_mean: bool) -> torch.Tensor:
+    """The ``loss_hp`` losses in torch ops, for logits rows ``x`` [R, V] and targets ``y`` [R]: F.cross_entropy with
+    label smoothing over the first C columns plus zeta x lse^2 (lse over all V columns) on the rows whose target lies
+    in [0, C); ``rows_mean``: divided by R, else by the number of such rows.  eps and zeta come from ``loss_hp``'s
+    host copy; ``loss_hp.nll`` is filled with the plain NLL under the same rule."""
+    eps, zeta = loss_hp.label_smoothing, loss_hp.z_loss
+    valid = (y >= 0) & (y < C)
+    y = torch.where(valid, y, torch.full_like(y, -100))
+    xc = x[..., :C].float()
+    rows = y.numel() if rows_mean else valid.sum().clamp_min(1)  # the fused pair's rule: no valid row gives 0, not NaN
+    loss = F.cross_entropy(xc, y, label_smoothing=eps, reduction="sum") / rows
+    with torch.no_grad():
+        loss_hp.nll.copy_(F.cross_entropy(xc, y, reduction="sum") / rows)
+    if zeta == 0.0:
+        return loss
+    return loss + zeta * ((torch.logsumexp(x.float(), dim=-1).square() * valid).sum() / rows)
+
+
+class _NextTokenXentHP(torch.autograd.Function):
+    """:class:`_NextTokenXent` with the loss's device hyper-parameters (ops/loss_hp.py; plx_xent_hp_fwd / _bwd): the
+    training loss lse - (1 - eps) x[t] - eps mean_{j<C} x[j] + zeta lse^2 with eps and zeta read from ``hp`` on the
+    device, C real classes of the V columns, and the mean plain NLL written into ``nll`` in place."""
+
+    @staticmethod
+    def forward(ctx, logits, tokens, hp, nll, C):
+        lib = _native.lib("plx_lm")
+        B, S, V = logits.shape
+        rows = B * (S - 1)
+        buf = [torch.empty(rows, dtype=torch.float32, device=logits.device) for _ in range(3)]  # lse, loss, nll
+        _native.check(lib.plx_xent_hp_fwd(logits.data_ptr(), tokens.data_ptr(), hp.data_ptr(), buf[0].data_ptr(),
+                                          buf[1].data_ptr(), buf[2].data_ptr(), B, S, V, C, _stream()),
+                      "plx_xent_hp_fwd")
+        ctx.save_for_backward(logits, tokens, buf[0], hp)
+        ctx.C = C
+        torch.mean(buf[2], dim=0, out=nll)
+        return buf[1].mean()
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _native.lib("plx_lm")
+        logits, tokens, lse, hp = ctx.saved_tensors
+        B, S, V = logits.shape
+        grad = torch.empty_like(logits)
+        g = g.detach().to(torch.float32).reshape(1).contiguous()
+        _native.check(lib.plx_xent_hp_bwd(logits.data_ptr(), tokens.data_ptr(), lse.data_ptr(), hp.data_ptr(),
+                                          g.data_ptr(), grad.data_ptr(), B, S, V, ctx.C, _stream()), "plx_xent_hp_bwd")
+        return grad, None, None, None, None
+
+
+def next_token_xent(logits: torch.Tensor, tokens: torch.Tensor, loss_hp=None,
+                    n_classes: Optional[int] = None) -> torch.Tensor:
     """Next-token cross entropy (targets = tokens shifted left), mean over B * (S - 1) positions: the fused HIP pair on
-    bf16 CUDA logits [B, S, V] (contiguous, 16-byte aligned) with int64 tokens [B, S]; the fp32 reference otherwise."""
-    if (logits.is_cuda and logits.dtype == torch.bfloat16 and logits.dim() == 3 and logits.is_contiguous()
-            and logits.data_ptr() % 16 == 0 and tokens.dtype == torch.int64 and tokens.is_contiguous()
-            and tokens.shape == logits.shape[:2] and logits.shape[1] >= 2):
+    bf16 CUDA logits [B, S, V] (contiguous, 16-byte aligned) with int64 tokens [B, S]; the fp32 reference otherwise.
+
+    ``loss_hp`` (ops/loss_hp.py LossHParams): the training loss with its label smoothing and z-loss, both device
+    data (plx_xent_hp_fwd / _bwd), over ``n_classes`` real classes (default V; columns beyond them are vocabulary
+    padding, targets there are ignored); ``loss_hp.nll`` receives the plain NLL.  None: the plain pair."""
+    native = (logits.is_cuda and logits.dtype == torch.bfloat16 and logits.dim() == 3 and logits.is_contiguous()
+              and logits.data_ptr() % 16 == 0 and tokens.dtype == torch.int64 and tokens.is_contiguous()
+              and tokens.shape == logits.shape[:2] and logits.shape[1] >= 2)
+    if loss_hp is not None:
+        C = _classes(n_classes, logits.shape[-1])
+        if native:
+            return _NextTokenXentHP.apply(logits, tokens, loss_hp.hp, loss_hp.nll, C)
+        return _xent_hp_reference(logits[:, :-1].reshape(-1, logits.shape[-1]), tokens[:, 1:].reshape(-1), loss_hp,
+                                  C, rows_mean=True)
+    if native:
         return _NextTokenXent.apply(logits, tokens)
     return F.cross_entropy(logits[:, :-1].reshape(-1, logits.shape[-1]).float(), tokens[:, 1:].reshape(-1))
 
@@ -220,13 +288,60 @@ class _ClassXent(torch.autograd.Function):
         return grad, None, None
 
 
-def class_xent(logits: torch.Tensor, labels: torch.Tensor, in_range: bool = False) -> torch.Tensor:
+class _ClassXentHP(torch.autograd.Function):
+    """:class:`_ClassXent` with the loss's device hyper-parameters (plx_xent_cls_hp_fwd / _bwd), as
+    :class:`_NextTokenXentHP`: a valid row is one whose label lies in [0, C)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, in_range, hp, nll, C):
+        lib = _native.lib("plx_lm")
+        N, V = logits.shape
+        buf = [torch.empty(N, dtype=torch.float32, device=logits.device) for _ in range(3)]  # lse, loss, nll
+        _native.check(lib.plx_xent_cls_hp_fwd(logits.data_ptr(), labels.data_ptr(), hp.data_ptr(), buf[0].data_ptr(),
+                                              buf[1].data_ptr(), buf[2].data_ptr(), N, V, C, _stream()),
+                      "plx_xent_cls_hp_fwd")
+        nvalid = None if in_range else ((labels >= 0) & (labels < C)).sum().clamp_min(1).to(torch.float32)
+        ctx.save_for_backward(logits, labels, buf[0], hp, nvalid if nvalid is not None else buf[0].new_ones(()))
+        ctx.in_range, ctx.C = in_range, C
+        if in_range:
+            torch.mean(buf[2], dim=0, out=nll)
+            return buf[1].mean()
+        torch.div(buf[2].sum(), nvalid, out=nll)
+        return buf[1].sum() / nvalid
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _native.lib("plx_lm")
+        logits, labels, lse, hp, nvalid = ctx.saved_tensors
+        N, V = logits.shape
+        grad = torch.empty_like(logits)
+        g = g.detach().to(torch.float32).reshape(1)
+        if not ctx.in_range:
+            g = g / nvalid  # scale 1: the kernel multiplies by dloss only
+        g = g.contiguous()
+        _native.check(lib.plx_xent_cls_hp_bwd(logits.data_ptr(), labels.data_ptr(), lse.data_ptr(), hp.data_ptr(),
+                                              g.data_ptr(), grad.data_ptr(), N, V, ctx.C,
+                                              0.0 if ctx.in_range else 1.0, _stream()), "plx_xent_cls_hp_bwd")
+        return grad, None, None, None, None, None
+
+
+def class_xent(logits: torch.Tensor, labels: torch.Tensor, in_range: bool = False, loss_hp=None,
+               n_classes: Optional[int] = None) -> torch.Tensor:
     """Classification cross entropy, mean over the rows with a label in [0, V) (F.cross_entropy semantics, ignore
     index -100 included): the fused HIP pair on bf16 CUDA logits [N, V] (contiguous) with int64 labels [N];
     F.cross_entropy on fp32 logits otherwise.  ``in_range``: the caller guarantees 0 <= label < V for every row
-    (skips the valid-row count)."""
-    if (logits.is_cuda and logits.dtype == torch.bfloat16 and logits.dim() == 2 and logits.is_contiguous()
-            and labels.dtype == torch.int64 and labels.is_contiguous() and labels.shape == logits.shape[:1]):
+    (skips the valid-row count).
+
+    ``loss_hp`` / ``n_classes``: as in :func:`next_token_xent` (plx_xent_cls_hp_fwd / _bwd); a valid row is then one
+    with a label in [0, n_classes), and ``in_range`` promises that of every row."""
+    native = (logits.is_cuda and logits.dtype == torch.bfloat16 and logits.dim() == 2 and logits.is_contiguous()
+              and labels.dtype == torch.int64 and labels.is_contiguous() and labels.shape == logits.shape[:1])
+    if loss_hp is not None:
+        C = _classes(n_classes, logits.shape[-1])
+        if native:
+            return _ClassXentHP.apply(logits, labels, bool(in_range), loss_hp.hp, loss_hp.nll, C)
+        return _xent_hp_reference(logits, labels, loss_hp, C, rows_mean=bool(in_range))
+    if native:
         return _ClassXent.apply(logits, labels, bool(in_range))
     return F.cross_entropy(logits.float(), labels)
 

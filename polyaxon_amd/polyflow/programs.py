@@ -18,9 +18,15 @@ Every built-in program also takes ``params: {lr_schedule: true | <kind>}``: the 
 ``min_lr_ratio``, ``lr_decay_gamma`` and ``lr_decay_every`` as per-trial hyper-parameters and ``lr`` as the base LR;
 ``true`` starts every trial at ``constant``.  A trial that names no ``lr_total_steps`` gets the horizon from the
 sweep driver (``params: {lr_horizon: max | rung}``, default ``max``; ops/lr_schedule.py horizon_steps).
+
+Every built-in program also takes ``params: {loss_hparams: true}``: ``label_smoothing`` and ``z_loss`` as per-trial
+hyper-parameters of the loss (ops/loss_hp.py), read from device memory by the fused cross-entropy kernels, both 0
+until a trial sets them.  The metric the program commits is then the plain NLL, not the training loss, so trials
+with different smoothing stay comparable.
 """
 from __future__ import annotations
 
+import functools
 import importlib
 import math
 from dataclasses import dataclass, field
@@ -57,6 +63,10 @@ class TrialProgram:
                 from polyaxon_amd.ops import lr_schedule as lrs
 
                 ex.set_hparams(**dict(lrs.DEFAULTS, lr_schedule=self.info["lr_schedule"]))
+            if self.info.get("loss_hparams"):  # back from the warm-up's smoothing and z-loss to none
+                from polyaxon_amd.ops import loss_hp
+
+                ex.set_hparams(**loss_hp.DEFAULTS)
         if ex.is_cuda:
             torch.cuda.synchronize(ex.device)
 
@@ -71,6 +81,22 @@ def _with_clip(prog: TrialProgram, clip: bool) -> TrialProgram:
         prog.hp_keys = prog.hp_keys + ("max_grad_norm",)
         prog.info["warm_hparams"] = {**prog.info.get("warm_hparams", {}), "max_grad_norm": 1.0}
         prog.info["clip_grad"] = True
+    return prog
+
+
+def _loss_hparams(params: Dict[str, Any]) -> bool:
+    return bool(params.get("loss_hparams", False))
+
+
+def _with_loss_hp(prog: TrialProgram, on: bool) -> TrialProgram:
+    """``loss_hparams`` programs understand ``label_smoothing`` and ``z_loss`` and warm up with both set, so the
+    warm steps run the full path."""
+    if on:
+        from polyaxon_amd.ops import loss_hp
+
+        prog.hp_keys = prog.hp_keys + loss_hp.KEYS
+        prog.info["warm_hparams"] = {**prog.info.get("warm_hparams", {}), "label_smoothing": 0.1, "z_loss": 1e-4}
+        prog.info["loss_hparams"] = True
     return prog
 
 
@@ -125,14 +151,14 @@ def _resnet(params: Dict[str, Any], device, tiny: bool) -> TrialProgram:
     model = resnet18ish(num_classes=classes) if tiny else resnet50(num_classes=classes)
     clip = _clip_grad(params)
     ex = ResidentTrialExecutor(model, data, dev, optimizer="sgd", use_graph=bool(params.get("graph", False)),
-                               clip_grad=clip, lr_schedule=_lr_schedule(params))
-    return _with_schedule(_with_clip(TrialProgram(
+                               clip_grad=clip, lr_schedule=_lr_schedule(params), loss_hparams=_loss_hparams(params))
+    return _with_loss_hp(_with_schedule(_with_clip(TrialProgram(
         ex, unit_steps=int(params.get("unit_steps", 1 if tiny else 4)),
         window=int(params.get("window", 4)), hp_keys=("lr", "momentum", "weight_decay", "nesterov"),
         info={"model": "resnet18ish" if tiny else "resnet50", "batch": batch, "image": image,
               "classes": classes, "data": "synthetic, fresh per step (ops/synth.py)",
               "warm_hparams": {"lr": 0.01, "momentum": 0.9, "weight_decay": 1e-4},
-              "images_per_step": batch}), clip), params)
+              "images_per_step": batch}), clip), params), _loss_hparams(params))
 
 
 def _mlp(params: Dict[str, Any], device) -> TrialProgram:
@@ -148,12 +174,12 @@ def _mlp(params: Dict[str, Any], device) -> TrialProgram:
     y = (x @ torch.randn(784, 10, generator=g)).argmax(1)
     clip = _clip_grad(params)
     ex = ResidentTrialExecutor(MLP(), (x, y), dev, optimizer="sgd", use_graph=dev.type == "cuda", channels_last=False,
-                               clip_grad=clip, lr_schedule=_lr_schedule(params))
-    return _with_schedule(_with_clip(TrialProgram(
+                               clip_grad=clip, lr_schedule=_lr_schedule(params), loss_hparams=_loss_hparams(params))
+    return _with_loss_hp(_with_schedule(_with_clip(TrialProgram(
         ex, unit_steps=int(params.get("unit_steps", 10)), window=int(params.get("window", 4)),
         hp_keys=("lr", "momentum", "weight_decay"),
         info={"model": "mlp", "batch": bs, "warm_hparams": {"lr": 0.01, "momentum": 0.9},
-              "images_per_step": bs}), clip), params)
+              "images_per_step": bs}), clip), params), _loss_hparams(params))
 
 
 def _gpt2(params: Dict[str, Any], device, tiny: bool) -> TrialProgram:
@@ -187,10 +213,14 @@ def _gpt2(params: Dict[str, Any], device, tiny: bool) -> TrialProgram:
     else:
         model = Transformer(cfg)
     clip = _clip_grad(params)
-    ex = ResidentTrialExecutor(model, data, dev, loss_fn=lm_loss, optimizer="adamw",
+    loss_hp = _loss_hparams(params)
+    # the smoothing term runs over the real vocabulary, not the -inf padding columns of the padded head
+    loss_fn = functools.partial(lm_loss, n_classes=cfg.vocab_size) if loss_hp else lm_loss
+    ex = ResidentTrialExecutor(model, data, dev, loss_fn=loss_fn, optimizer="adamw",
                                use_graph=bool(params.get("graph", False)), channels_last=False,
-                               lp_dtype=torch.bfloat16, clip_grad=clip, lr_schedule=_lr_schedule(params))
-    return _with_schedule(_with_clip(TrialProgram(
+                               lp_dtype=torch.bfloat16, clip_grad=clip, lr_schedule=_lr_schedule(params),
+                               loss_hparams=loss_hp)
+    return _with_loss_hp(_with_schedule(_with_clip(TrialProgram(
         ex, unit_steps=int(params.get("unit_steps", 4 if tiny else 10)),
         window=int(params.get("window", 4)),
         hp_keys=("lr", "beta1", "beta2", "eps", "weight_decay"),
@@ -200,7 +230,7 @@ def _gpt2(params: Dict[str, Any], device, tiny: bool) -> TrialProgram:
                                "weight_decay": 0.1},
               "tokens_per_step": batch * seq, "floor_loss": data.floor_loss,
               "unigram_loss": data.unigram_loss, "chance_loss": data.chance_loss,
-              "active_vocab": data.active_vocab}), clip), params)
+              "active_vocab": data.active_vocab}), clip), params), loss_hp)
 
 
 PROGRAMS: Dict[str, Callable[[Dict[str, Any], Any], TrialProgram]] = {

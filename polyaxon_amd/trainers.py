@@ -70,6 +70,15 @@ def _schedule_hparams(args, total_steps: int) -> dict:
             "lr_decay_every": args.lr_decay_every}
 
 
+def _loss_args(ap: argparse.ArgumentParser) -> None:
+    """Label smoothing and z-loss of the resnet and lm trainers (ops/loss_hp.py); both 0: the plain loss, with
+    nothing of the feature built."""
+    ap.add_argument("--label_smoothing", type=float, default=0.0,
+                    help="label smoothing of the fused cross entropy, in [0, 1); the reported loss stays the plain NLL")
+    ap.add_argument("--z_loss", type=float, default=0.0,
+                    help="z-loss weight: adds z_loss x logsumexp(logits)^2 per position to the training loss")
+
+
 def _parse(ap: argparse.ArgumentParser, argv):
     args = ap.parse_args(argv)
     args._defaults = {a.dest: a.default for a in ap._actions}
@@ -156,6 +165,7 @@ def train_resnet(argv=None) -> float:
     ap.add_argument("--units", type=int, default=1)
     ap.add_argument("--unit_steps", type=int, default=8)
     _schedule_args(ap, warmup=True)
+    _loss_args(ap)
     args = _parse(ap, argv)
     dev = _device(args)
     g = torch.Generator().manual_seed(args.seed)
@@ -166,7 +176,9 @@ def train_resnet(argv=None) -> float:
     y = torch.randint(0, 1000, (args.bs,), generator=g)
     clip = args.max_grad_norm > 0
     sched = args.lr_schedule != "none"
-    ex = ResidentTrialExecutor(resnet50(), (x, y), dev, use_graph=False, clip_grad=clip, lr_schedule=sched)
+    loss_hp = args.label_smoothing != 0 or args.z_loss != 0
+    ex = ResidentTrialExecutor(resnet50(), (x, y), dev, use_graph=False, clip_grad=clip, lr_schedule=sched,
+                               loss_hparams=loss_hp)
     ckpt = _ckpt_path() if args.ckpt else None
     done_units = 0
     ex.reset(seed=args.seed)
@@ -177,9 +189,10 @@ def train_resnet(argv=None) -> float:
         ex.buffers.copy_(st["buffers"])
         ex.step.fill_(int(st["step"]))
         done_units = int(st["units"])
-    # (the executor passes on only what its optimizer knows: max_grad_norm exists when clipping is on)
+    # (the executor passes on only what it knows: max_grad_norm exists when clipping is on, the loss's two when the
+    # loss hyper-parameters are)
     ex.set_hparams(lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay,
-                   max_grad_norm=args.max_grad_norm)
+                   max_grad_norm=args.max_grad_norm, label_smoothing=args.label_smoothing, z_loss=args.z_loss)
     if sched:  # the horizon is the trial's full resource: a RESUMEd rung continues the curve at its restored step
         ex.set_hparams(**_schedule_hparams(args, args.units * args.unit_steps))
     ex.run(max(0, args.units - done_units) * args.unit_steps)
@@ -191,6 +204,8 @@ def train_resnet(argv=None) -> float:
                     "step": int(ex.step.item()), "units": args.units}, ckpt)
     xp = _tracker()
     lr_out = {"lr": float(ex.current_lr())} if sched else {}
+    if loss_hp:  # `loss` is the plain NLL then
+        lr_out["train_loss"] = float(ex.train_loss())
     if xp is not None:
         xp.log_metrics(step=int(ex.step.item()), loss=loss, **lr_out)
         xp.close()
@@ -230,6 +245,7 @@ def train_lm(argv=None) -> float:
                     help="ZeRO-1: reduce-scatter each gradient bucket, AdamW on this rank's 1/W slice inside the "
                          "backward, all-gather the bf16 weights (parallel/ddp.py); also PLX_ZERO1=1")
     _schedule_args(ap, warmup=False)  # --warmup_steps above: host-side without a schedule, the schedule's with one
+    _loss_args(ap)
     args = _parse(ap, argv)
     clip = args.max_grad_norm > 0
     sched = args.lr_schedule != "none"
@@ -279,6 +295,12 @@ def train_lm(argv=None) -> float:
     ddp = FlatDDP(flat, bucket_mb=args.bucket_mb, optimizer=opt if in_bwd else None, shard_optimizer=zero1,
                   force_collectives=force_buckets)
     ddp.broadcast_params()
+    loss_hp = None
+    if args.label_smoothing != 0 or args.z_loss != 0:  # device data of the fused loss; 0 / 0: not built at all
+        from polyaxon_amd.ops.loss_hp import LossHParams
+
+        loss_hp = LossHParams(dev)
+        loss_hp.set(label_smoothing=args.label_smoothing, z_loss=args.z_loss)
     metrics = MetricReducer(dev, force_comm=force)  # cross-rank mean of the logged loss (RCCL communicator, GPU)
     g = torch.Generator(device=dev).manual_seed(args.seed + 1000 * info["rank"])
 
@@ -312,18 +334,26 @@ def train_lm(argv=None) -> float:
         if it and not args.fixed_batch:
             tokens = batch()
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
-            loss = lm_loss(model(tokens), tokens)
+            if loss_hp is None:
+                loss = lm_loss(model(tokens), tokens)
+            else:  # trains on the smoothed loss; the logged one is the plain NLL the loss leaves in loss_hp.nll
+                loss = lm_loss(model(tokens), tokens, loss_hp=loss_hp, n_classes=cfg.vocab_size)
         loss.backward()
         ddp.finish()
         opt.step_()
         step += 1
         if (it + 1) % args.log_every == 0 or it == args.steps - 1:
+            train_loss = loss
+            if loss_hp is not None:
+                loss = loss_hp.nll
             loss_mean = metrics.mean(loss)  # every rank joins the collective; rank 0 logs it
             if xp is not None and (it + 1) % args.log_every == 0:
                 # the norm of the averaged gradients is the same on every rank: no reduction of its own
                 extra = {"grad_norm": opt.grad_norm().clone()} if clip else {}
                 if sched:
                     extra["lr"] = opt.current_lr().clone()
+                if loss_hp is not None:
+                    extra["train_loss"] = train_loss.detach().clone()
                 xp.log_metrics(step=it + 1, loss=loss_mean[0], **extra)
             if it == args.steps - 1:
                 loss_val = float(loss_mean[0])
