@@ -13,9 +13,9 @@
 // sub-tile computed with v_mfma_f32_16x16x32_bf16; tiles are staged global -> LDS with 16-byte
 // global_load_lds (LDS image lane-linear, bank swizzle applied on the per-lane SOURCE address and on the
 // read, rule 21), double-buffered over BK = 64; blockIdx is remapped so blocks sharing an operand panel
-// run on one XCD (T1, bijective form).  The NT GEMM stages through buffer-resource LDS-DMA: rows past the end
+// run on one XCD (T1, bijective form).  Every GEMM stages through buffer-resource LDS-DMA: rows past the end
 // of M and the taps of a convolution that fall outside the image get an out-of-range offset and read zeros, so
-// partial tiles and padding need no branches around the DMA; the TN GEMM reads a zero page instead.
+// partial tiles and padding need no branches around the DMA.
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
@@ -34,8 +34,8 @@ constexpr int BK = 64;          // reduction depth per LDS stage (bf16 elements)
 // Implicit-GEMM geometry of a convolution on NHWC rows (1x1 or 3x3, stride 1 or 2).
 // GEMM rows are pixels of a row grid (Hr x Wr per image): row m = (n*Hr + r)*Wr + c.  The reduction index is
 // k = t*C + ch over `ntaps` taps; for tap t the operand row is the source pixel (r*S + offh[t], c*S + offw[t])
-// of an H x W image (out-of-image -> the zero page, i.e. the zero padding), and the B operand column is
-// btap[t]*C + ch (B holds all 9 (or 1) taps).  Forward / weight-gradient use S = stride, off = tap - pad;
+// of an H x W image (out-of-image -> an out-of-range buffer offset, which reads zeros: the zero padding), and the B
+// operand column is btap[t]*C + ch (B holds all 9 (or 1) taps).  Forward / weight-gradient use S = stride, off = tap - pad;
 // the stride-1 data gradient flips the taps (off = pad - tap); the stride-2 data gradient is split into the
 // four (ih, iw) parity classes of the input, each a stride-1 gather over the taps of matching parity, whose
 // output rows are scattered back to input pixels (2r + ph, 2c + pw) of an Hc x Wc grid (OS = 2).
@@ -181,8 +181,8 @@ __device__ __forceinline__ void glds16(const void* g, void* l) {
 }
 
 // LDS-DMA through a buffer resource: base and range live in SGPRs, each lane supplies a 32-bit byte offset, and an
-// offset at or past the range (OOB) returns zeros -- the zero padding of a convolution costs one select, no
-// zero page and no 64-bit address math.  Operands here are < 2 GiB, so the range is 2^31 bytes.
+// offset at or past the range (OOB) returns zeros -- the zero padding of a convolution costs one select and no
+// 64-bit address math.  Operands here are < 2 GiB, so the range is 2^31 bytes.
 constexpr uint32_t OOB = 0x80000000u;
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc(const void* base) {
@@ -226,9 +226,9 @@ template <int BM, int BN, int WGM, int WGN, int MODE, int MINB = 2, int NBUF = 2
           bool BNDX = false, int BNAP = 0>
 __global__ void __launch_bounds__(NTH, MINB)
 gemm_nt_kernel(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf16* __restrict__ C,
-               int M, int N, int K, int lda, int ldb, int ldc, const __bf16* __restrict__ zero,
-               float* __restrict__ stats, ConvGeom geo, const __bf16* __restrict__ D, int ldd, BnBwd bnr,
-               const uint8_t* __restrict__ dmask, BnDx bd, BnApply ba) {
+               int M, int N, int K, int lda, int ldb, int ldc, float* __restrict__ stats, ConvGeom geo,
+               const __bf16* __restrict__ D, int ldd, BnBwd bnr, const uint8_t* __restrict__ dmask, BnDx bd,
+               BnApply ba) {
     constexpr bool CONV = MODE == 1, STEM = MODE == 2;
     constexpr bool PROD = BNDX || BNAP != 0;               // the kernel produces its A operand
     static_assert(BNAP >= 0 && BNAP <= 2 && !(BNDX && BNAP != 0), "one producer mode");
@@ -253,9 +253,9 @@ gemm_nt_kernel(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf1
 
     // Staging addresses, fixed over the whole k loop: each A row this thread stages gets its element offset
     // (with the lane's swizzled 16-B chunk folded in) and, in conv mode, a bit per tap saying whether that tap's
-    // source pixel is inside the image (else the zero page is read: the zero padding).  A stage then costs one
-    // bit test, one add and a select per row -- the per-stage bounds checks and 64-bit address math were ~20
-    // VALU per row and, beside 32 MFMAs per wave and stage, set the loop's pace.
+    // source pixel is inside the image (else the offset is OOB and zeros are read: the zero padding).  A stage then
+    // costs one bit test, one add and a select per row -- the per-stage bounds checks and 64-bit address math were
+    // ~20 VALU per row and, beside 32 MFMAs per wave and stage, set the loop's pace.
     constexpr int AI = BM / (8 * NW), BI = BN / (8 * NW);  // LDS-DMA instructions per wave per stage (A, B)
     int a_off[AI];                                          // byte offsets
     uint32_t a_ok[AI];
@@ -859,8 +859,7 @@ __device__ __forceinline__ void stage_rows(char* img, __amdgpu_buffer_rsrc_t rsr
 template <int BN1, int BN2, int WG1, int WG2, int CONV, int NST = 2, int BKT = BK>
 __global__ void __launch_bounds__(NTHREADS, NST * BKT <= 2 * BK ? 2 : 1)
 gemm_tn_kernel(const __bf16* __restrict__ A, const __bf16* __restrict__ B, float* __restrict__ W,
-               int M, int N1, int N2, int lda, int ldb, int kchunk, const __bf16* __restrict__ zero,
-               ConvGeom geo) {
+               int M, int N1, int N2, int lda, int ldb, int kchunk, ConvGeom geo) {
     constexpr int WT1 = BN1 / WG1, WT2 = BN2 / WG2, R1 = WT1 / 16, R2 = WT2 / 16;
     constexpr int ROWA = BN1 * 2, ROWB_ = BN2 * 2;
     constexpr int A_BYTES = BKT * ROWA, STAGE = BKT * (ROWA + ROWB_);
@@ -1311,9 +1310,9 @@ int set_lds(KernelT k, int bytes) {
 
 // NBUF = 1: one K-stage buffer, LDS = max(stage, epilogue staging), 3-4 blocks per CU (the skinny GEMMs)
 template <int BM, int BN, int WGM, int WGN, int CONV = 0, int NBUF = 2>
-int launch_nt(const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb, int ldc,
-              const void* zero, float* stats, hipStream_t s, ConvGeom geo = {}, const void* D = nullptr,
-              int ldd = 0, BnBwd bnr = {}, const uint8_t* dmask = nullptr) {
+int launch_nt(const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb, int ldc, float* stats,
+              hipStream_t s, ConvGeom geo = {}, const void* D = nullptr, int ldd = 0, BnBwd bnr = {},
+              const uint8_t* dmask = nullptr) {
     constexpr int NTH = NTHREADS;
     constexpr int TILE = BM * (BN * 2 + 16), RED = NTH * 17 * 4;
     constexpr int EPI = TILE > RED ? TILE : RED;            // the reduction reuses the tile's LDS
@@ -1337,44 +1336,29 @@ int launch_nt(const void* A, const void* B, void* C, int M, int N, int K, int ld
     auto k = bwd ? kb : kf;
     const int nwg = ((M + BM - 1) / BM) * (N / BN);
     hipLaunchKernelGGL(k, dim3(nwg), dim3(NTH), LDS, s, (const __bf16*)A, (const __bf16*)B, (__bf16*)C, M, N,
-                       K, lda, ldb, ldc, (const __bf16*)zero, stats, geo, (const __bf16*)D, ldd, bnr, dmask, BnDx{}, BnApply{});
+                       K, lda, ldb, ldc, stats, geo, (const __bf16*)D, ldd, bnr, dmask, BnDx{}, BnApply{});
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
-// The data-gradient GEMM that produces its A operand, a BatchNorm backward's dx (BnDx), double-buffered at 2 blocks
-// per CU.  g = the BatchNorm's incoming gradient (the kernel's A pointer), dense like bd.x and bd.dy (ld = K).
-template <int BM, int BN, int WGM, int WGN>
-int launch_nt_bndx(const void* g, const BnDx& bd, const void* B, void* C, int M, int N, int K, int ldb, int ldc,
-                   hipStream_t s, const void* D, int ldd, BnBwd bnr, const uint8_t* dmask) {
+// The GEMMs that produce their A operand, double-buffered at 2 blocks per CU: the data gradient whose A is a BatchNorm
+// backward's dx (BNDX: bd, and the data-gradient epilogue's D / ldd / bnr / dmask; A = the BatchNorm's incoming
+// gradient), or the forward whose A is a BatchNorm apply + residual + ReLU (BNAP 1 / 2: ba, and stats; A = the
+// BatchNorm's raw input).  A is dense like the tensors of bd / ba (ld = K).  The tiles are plx_gemm_nt's, so C and
+// the stats partials keep their values, layout and summation order.
+template <int BM, int BN, int WGM, int WGN, bool BNDX, int BNAP>
+int launch_nt_prod(const void* A, const BnDx& bd, const BnApply& ba, const void* B, void* C, int M, int N, int K,
+                   int ldb, int ldc, float* stats, hipStream_t s, const void* D = nullptr, int ldd = 0, BnBwd bnr = {},
+                   const uint8_t* dmask = nullptr) {
     constexpr int TILE = BM * (BN * 2 + 16), RED = NTHREADS * 17 * 4;
     constexpr int LDS = 2 * (BM + BN) * BK * 2;
     static_assert(TILE <= LDS && RED <= LDS && LDS <= 80 * 1024, "epilogue staging fits; 2 blocks per CU");
-    auto k = gemm_nt_kernel<BM, BN, WGM, WGN, 0, 2, 2, true, NTHREADS, true>;
+    static_assert(BNDX != (BNAP != 0), "exactly one producer mode");
+    auto k = gemm_nt_kernel<BM, BN, WGM, WGN, 0, 2, 2, BNDX, NTHREADS, BNDX, BNAP>;
     static int attr = set_lds(k, LDS);
     if (attr) return attr;
     const int nwg = ((M + BM - 1) / BM) * (N / BN);
-    hipLaunchKernelGGL(k, dim3(nwg), dim3(NTHREADS), LDS, s, (const __bf16*)g, (const __bf16*)B, (__bf16*)C, M, N, K, K,
-                       ldb, ldc, (const __bf16*)nullptr, (float*)nullptr, ConvGeom{}, (const __bf16*)D, ldd, bnr, dmask,
-                       bd, BnApply{});
-    return hipGetLastError() == hipSuccess ? 0 : -3;
-}
-
-// The forward GEMM that produces its A operand, a BatchNorm apply + residual + ReLU (BnApply), double-buffered at 2
-// blocks per CU.  x = the BatchNorm's raw input (the kernel's A pointer), dense like ba.res and ba.out (ld = K).  The
-// tiles are plx_gemm_nt's, so y and the stats partials keep their values, layout and summation order.
-template <int BM, int BN, int WGM, int WGN, int BNAP>
-int launch_nt_bnapply(const void* x, const BnApply& ba, const void* B, void* C, int M, int N, int K, int ldb, int ldc,
-                      float* stats, hipStream_t s) {
-    constexpr int TILE = BM * (BN * 2 + 16), RED = NTHREADS * 17 * 4;
-    constexpr int LDS = 2 * (BM + BN) * BK * 2;
-    static_assert(TILE <= LDS && RED <= LDS && LDS <= 80 * 1024, "epilogue staging fits; 2 blocks per CU");
-    auto k = gemm_nt_kernel<BM, BN, WGM, WGN, 0, 2, 2, false, NTHREADS, false, BNAP>;
-    static int attr = set_lds(k, LDS);
-    if (attr) return attr;
-    const int nwg = ((M + BM - 1) / BM) * (N / BN);
-    hipLaunchKernelGGL(k, dim3(nwg), dim3(NTHREADS), LDS, s, (const __bf16*)x, (const __bf16*)B, (__bf16*)C, M, N, K, K,
-                       ldb, ldc, (const __bf16*)nullptr, stats, ConvGeom{}, (const __bf16*)nullptr, 0, BnBwd{},
-                       (const uint8_t*)nullptr, BnDx{}, ba);
+    hipLaunchKernelGGL(k, dim3(nwg), dim3(NTHREADS), LDS, s, (const __bf16*)A, (const __bf16*)B, (__bf16*)C, M, N, K, K,
+                       ldb, ldc, stats, ConvGeom{}, (const __bf16*)D, ldd, bnr, dmask, bd, ba);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
@@ -1394,13 +1378,32 @@ inline void tn_tile(int N1, int N2, int& bn1, int& bn2) {
     bn2 = N2 % 128 == 0 ? 128 : 64;
 }
 
+// slab reducer sizing (shared by both plans): ~1024 blocks; many slabs are first summed in groups of >= 8 so a small
+// plane still spreads out
+inline void plan_reducer(TnPlan& p, long plane) {
+    const long total4 = plane / 4;
+    int blocks = (int)((total4 + 255) / 256);
+    if (blocks > 2048) blocks = 2048;
+    int groups = 1024 / blocks;
+    if (groups > p.slices / 8) groups = p.slices / 8;
+    if (groups < 1) groups = 1;
+    const int per_group = (p.slices + groups - 1) / groups;
+    p.groups = (p.slices + per_group - 1) / per_group;
+    p.per_group = per_group;
+    p.blocks = blocks;
+}
+
+// fp32 slab planes a plan's workspace holds: one per slice, and one per reducer group when the slabs are summed in two
+// passes
+inline long plan_slabs(const TnPlan& p) { return p.slices + (p.groups > 1 ? p.groups : 0); }
+
 // v1 slicing: target resident blocks per CU, cap on the fp32 slab bytes.  (v1 serves the stem's weight gradient, alone
-// at the end of the backward with 4 blocks per CU, and the v1 variant of the tests.)  Swept in isolation (scripts/diag_wgrad_plan.py) 3 / 32 MB was best; in the training step the weight gradients run on
-// the side stream beside the data-gradient chain, and there fewer slices (less slab traffic competing with the main
-// stream) win, except for the 56x56 layers whose gradients finish the backward: 0 = by size (tn_plan), 16 MB.  Same-box
-// bench, 2 interleaved rounds (blocks per CU / slab MB): 3/32 11.61k, 11.70k; 1/16 11.71k, 11.75k; by size 11.85k, 11.87k trials/h.
-// Slab cap under the by-size plan: 8 MB 10.62k / 10.60k (too few slices), 16 MB 11.92k / 11.93k, 32 MB 11.91k / 11.91k
-constexpr int g_tn_blocks_per_cu = 0;
+// at the end of the backward with 4 blocks per CU, and the v1 variant of the tests.)  Swept in isolation 3 blocks per CU
+// / 32 MB was best; in the training step the weight gradients run on the side stream beside the data-gradient chain,
+// and there fewer slices (less slab traffic competing with the main stream) win, except for the 56x56 layers whose
+// gradients finish the backward: blocks per CU by size (tn_plan), 16 MB.  Same-box bench, 2 interleaved rounds (blocks
+// per CU / slab MB): 3/32 11.61k, 11.70k; 1/16 11.71k, 11.75k; by size 11.85k, 11.87k trials/h.  Slab cap under the
+// by-size plan: 8 MB 10.62k / 10.60k (too few slices), 16 MB 11.92k / 11.93k, 32 MB 11.91k / 11.91k
 constexpr int g_tn_bpc_big = 3, g_tn_bpc_mid = 1;  // by-size plan: 56x56 layers, 28x28 layers
 constexpr long g_tn_slab_bytes = 16l << 20;
 
@@ -1410,13 +1413,10 @@ inline TnPlan tn_plan(int M, int N1, int N2, int num_cus, int bpc = 0) {
     tn_tile(N1, N2, bn1, bn2);
     const int ntiles = (N1 / bn1) * (N2 / bn2);
     const long plane = (long)N1 * N2;
-    // ~4 blocks per CU (one 4-wave block per CU leaves each SIMD a single wave: latency-bound), >= 4
-    // k-stages per block, slabs <= 32 MB (they are re-read by the reducer, mostly from the infinity cache)
-    // g_tn_blocks_per_cu == 0: by size -- the 56x56 layers (M >= 400k rows) are the last weight gradients of the
-    // backward, with little main-stream work left to hide them behind, so they get 3 blocks per CU; the rest 1
-    const int bpc_eff = bpc > 0 ? bpc
-                                : (g_tn_blocks_per_cu > 0 ? g_tn_blocks_per_cu
-                                                          : (M >= 400000 ? g_tn_bpc_big : M >= 150000 ? g_tn_bpc_mid : 1));
+    // blocks per CU by size: the 56x56 layers (M >= 400k rows) are the last weight gradients of the backward, with
+    // little main-stream work left to hide them behind, so they get 3 blocks per CU; the rest 1.  >= 4 k-stages per
+    // block, slabs <= 16 MB (they are re-read by the reducer, mostly from the infinity cache)
+    const int bpc_eff = bpc > 0 ? bpc : (M >= 400000 ? g_tn_bpc_big : M >= 150000 ? g_tn_bpc_mid : 1);
     int slices = (bpc_eff * (num_cus > 0 ? num_cus : 256)) / ntiles;
     const int by_depth = M / (4 * BK);
     const int by_bytes = (int)(g_tn_slab_bytes / (plane * 4));
@@ -1425,22 +1425,14 @@ inline TnPlan tn_plan(int M, int N1, int N2, int num_cus, int bpc = 0) {
     if (slices < 1) slices = 1;
     int kchunk = (M + slices - 1) / slices;
     kchunk = ((kchunk + BK - 1) / BK) * BK;
-    slices = (M + kchunk - 1) / kchunk;
-    // reducer: ~1024 blocks; many slabs are first summed in groups of >= 8 so a small plane still spreads out
-    const long total4 = plane / 4;
-    int blocks = (int)((total4 + 255) / 256);
-    if (blocks > 2048) blocks = 2048;
-    int groups = 1024 / blocks;
-    if (groups > slices / 8) groups = slices / 8;
-    if (groups < 1) groups = 1;
-    const int per_group = (slices + groups - 1) / groups;
-    groups = (slices + per_group - 1) / per_group;
-    return {kchunk, slices, groups, per_group, blocks, bn1, bn2};
+    TnPlan p{kchunk, (M + kchunk - 1) / kchunk, 1, 1, 0, bn1, bn2};
+    plan_reducer(p, plane);
+    return p;
 }
 
 template <int BN1, int BN2, int WG1, int WG2, int CONV, int NST, int BKT = BK>
 int launch_tn_st(const void* A, const void* B, float* W, int M, int N1, int N2, int lda, int ldb, const TnPlan& plan,
-                 const void* zero, hipStream_t s, const ConvGeom& geo) {
+                 hipStream_t s, const ConvGeom& geo) {
     constexpr int LDS = NST * BKT * (BN1 + BN2) * 2;
     static_assert(LDS <= 160 * 1024, "LDS ring exceeds the CU's LDS");
     auto k = gemm_tn_kernel<BN1, BN2, WG1, WG2, CONV, NST, BKT>;
@@ -1448,7 +1440,7 @@ int launch_tn_st(const void* A, const void* B, float* W, int M, int N1, int N2, 
     if (attr) return attr;
     const int ntiles = (N1 / BN1) * (N2 / BN2);
     hipLaunchKernelGGL(k, dim3(ntiles * plan.slices), dim3(NTHREADS), LDS, s, (const __bf16*)A, (const __bf16*)B, W,
-                       M, N1, N2, lda, ldb, plan.kchunk, (const __bf16*)zero, geo);
+                       M, N1, N2, lda, ldb, plan.kchunk, geo);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
@@ -1475,20 +1467,6 @@ inline V2Cfg v2_cfg(int N1, int N2) {
     return N1 % 256 == 0 ? V2Cfg{4, 1, 2} : V2Cfg{2, 1, 4};  // N2 an odd multiple of 64
 }
 
-// slab reducer sizing (shared by both plans): ~1024 blocks; many slabs are first summed in groups of >= 8
-inline void plan_reducer(TnPlan& p, long plane) {
-    const long total4 = plane / 4;
-    int blocks = (int)((total4 + 255) / 256);
-    if (blocks > 2048) blocks = 2048;
-    int groups = 1024 / blocks;
-    if (groups > p.slices / 8) groups = p.slices / 8;
-    if (groups < 1) groups = 1;
-    const int per_group = (p.slices + groups - 1) / groups;
-    p.groups = (p.slices + per_group - 1) / per_group;
-    p.per_group = per_group;
-    p.blocks = blocks;
-}
-
 // Slices: the grid runs one block per CU, so slices s put ceil(tiles * s / CUs) blocks on the busiest CU.  Modelled
 // time = compute (FLOP / chip rate, stretched by that quantisation) + a per-block fixed cost (ring fill + epilogue)
 // per round of blocks + the slab bytes (s + 1 planes: written, read back by the reducer) when s > 1.  Rates are
@@ -1508,11 +1486,6 @@ inline int tn2_ring_kb(const V2Cfg& c) {
     return g_tn2_lds_kb <= 64 && tn2_ring(c.na, c.nb, c.ks, 64) ? 64 : 128;
 }
 
-// blocks the v2 plan aims for: 1 or 2 per CU, or (> 2) a total block count; 0 (default): 3/4 of the CUs, which leaves
-// a quarter of the CUs whole to the main stream's kernels (in-step sweep over 128-256 blocks: 192 best, 176 / 208 /
-// 224 / 256 at or below v1)
-constexpr int g_tn2_bpc = 0;
-
 // the stem's weight gradient (CONV 2), which runs alone on the main stream at the very end of the backward: 0 v1
 // (gemm_tn_kernel, 4 blocks per CU), 1 v2 planned for 2 blocks on every CU, 2 v2 with the side stream's block target
 // (test hook plx_set_tn2_stem)
@@ -1528,16 +1501,14 @@ constexpr int kStemV2Bpc = 2;
 // plx_set_tn_atomic (PLX_WGRAD_ATOMIC)
 int g_tn_atomic = 1;
 
-// full_bpc > 0: plan for that many blocks on EVERY CU (the stem's weight gradient, alone on the GPU at the end of the
-// backward), whatever the block target
+// Blocks the plan aims for: 3/4 of the CUs, which leaves a quarter of the CUs whole to the main stream's kernels
+// (in-step sweep over 128-256 blocks: 192 best, 176 / 208 / 224 / 256 at or below v1).  full_bpc > 0: that many blocks
+// on EVERY CU instead (the stem's weight gradient, alone on the GPU at the end of the backward)
 inline TnPlan tn2_plan(int M, int N1, int N2, int num_cus, const V2Cfg& c, int full_bpc = 0) {
     const int bn1 = 64 * c.na, bn2 = 64 * c.nb;
     const int ntiles = (N1 / bn1) * (N2 / bn2);
     const int ncu = num_cus > 0 ? num_cus : 256;
-    const int cus = full_bpc > 0     ? ncu * full_bpc
-                    : g_tn2_bpc > 2  ? g_tn2_bpc
-                    : g_tn2_bpc > 0  ? ncu * g_tn2_bpc
-                                     : (ncu * 3) / 4;
+    const int cus = full_bpc > 0 ? ncu * full_bpc : (ncu * 3) / 4;
     const int step = 32 * c.ks;                       // rows per iteration
     const long plane = (long)N1 * N2;
     const double flops = 2.0 * M * plane;
@@ -1610,10 +1581,10 @@ int dispatch_tn2(const V2Cfg& c, const void* A, const void* B, float* W, int M, 
 
 template <int BN1, int BN2, int WG1, int WG2, int CONV = 0>
 int launch_tn(const void* A, const void* B, float* W, int M, int N1, int N2, int lda, int ldb, const TnPlan& plan,
-              const void* zero, hipStream_t s, ConvGeom geo = {}) {
+              hipStream_t s, ConvGeom geo = {}) {
     // double buffering (deeper rings measured slower in the step: a 96-128 KB ring leaves no LDS on its CU for the
     // data-gradient chain's blocks, profiles/r3_negative_results.md)
-    return launch_tn_st<BN1, BN2, WG1, WG2, CONV, 2>(A, B, W, M, N1, N2, lda, ldb, plan, zero, s, geo);
+    return launch_tn_st<BN1, BN2, WG1, WG2, CONV, 2>(A, B, W, M, N1, N2, lda, ldb, plan, s, geo);
 }
 
 }  // namespace
@@ -1628,8 +1599,7 @@ int plx_gemm_nt_rows_per_block(int N) { return N % 128 == 0 ? 128 : 256; }
 // bnr (nullable host struct): fused BatchNorm-backward partials of C (see BnBwd; needs ldc == N)
 // dmask (nullable, needs D and ldd == N): D is added where its bit is set (D * ReLU mask, 1 bit per element)
 int plx_gemm_nt(const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb, int ldc,
-                const void* zero, float* stats, const void* D, int ldd, const uint8_t* dmask, const BnBwd* bnr,
-                void* stream) {
+                float* stats, const void* D, int ldd, const uint8_t* dmask, const BnBwd* bnr, void* stream) {
     if (M <= 0 || N % 64 || K % BK || lda % 8 || ldb % 8 || ldc % 8 || (D != nullptr && ldd % 8)) return -1;
     if (dmask != nullptr && (D == nullptr || ldd != N)) return -1;
     if (bnr != nullptr && (ldc != N || bnr->part == nullptr)) return -1;
@@ -1637,13 +1607,12 @@ int plx_gemm_nt(const void* A, const void* B, void* C, int M, int N, int K, int 
     hipStream_t s = (hipStream_t)stream;
     if (N % 128 == 0) {
         const bool one = nt_single(false, K, ((M + 127) / 128) * (N / 128));
-        return one ? launch_nt<128, 128, 2, 2, false, 1>(A, B, C, M, N, K, lda, ldb, ldc, zero, stats, s, {}, D, ldd, b,
-                                                         dmask)
-                   : launch_nt<128, 128, 2, 2>(A, B, C, M, N, K, lda, ldb, ldc, zero, stats, s, {}, D, ldd, b, dmask);
+        return one ? launch_nt<128, 128, 2, 2, false, 1>(A, B, C, M, N, K, lda, ldb, ldc, stats, s, {}, D, ldd, b, dmask)
+                   : launch_nt<128, 128, 2, 2>(A, B, C, M, N, K, lda, ldb, ldc, stats, s, {}, D, ldd, b, dmask);
     }
     const bool one = nt_single(false, K, ((M + 255) / 256) * (N / 64));
-    return one ? launch_nt<256, 64, 4, 1, false, 1>(A, B, C, M, N, K, lda, ldb, ldc, zero, stats, s, {}, D, ldd, b, dmask)
-               : launch_nt<256, 64, 4, 1>(A, B, C, M, N, K, lda, ldb, ldc, zero, stats, s, {}, D, ldd, b, dmask);
+    return one ? launch_nt<256, 64, 4, 1, false, 1>(A, B, C, M, N, K, lda, ldb, ldc, stats, s, {}, D, ldd, b, dmask)
+               : launch_nt<256, 64, 4, 1>(A, B, C, M, N, K, lda, ldb, ldc, stats, s, {}, D, ldd, b, dmask);
 }
 
 // Data gradient of a 1x1 convolution whose incoming gradient is a BatchNorm backward's dx, produced in the kernel:
@@ -1664,8 +1633,9 @@ int plx_gemm_nt_bndx(const void* g, const void* x, const uint8_t* mask, const fl
     const BnBwd b = bnr != nullptr ? *bnr : BnBwd{};
     const BnDx bd{(const __bf16*)x, mask, coef, (__bf16*)dy};
     hipStream_t s = (hipStream_t)stream;
-    if (N % 128 == 0) return launch_nt_bndx<128, 128, 2, 2>(g, bd, Wt, C, M, N, K, ldb, ldc, s, D, ldd, b, dmask);
-    return launch_nt_bndx<256, 64, 4, 1>(g, bd, Wt, C, M, N, K, ldb, ldc, s, D, ldd, b, dmask);
+    if (N % 128 == 0)
+        return launch_nt_prod<128, 128, 2, 2, true, 0>(g, bd, {}, Wt, C, M, N, K, ldb, ldc, nullptr, s, D, ldd, b, dmask);
+    return launch_nt_prod<256, 64, 4, 1, true, 0>(g, bd, {}, Wt, C, M, N, K, ldb, ldc, nullptr, s, D, ldd, b, dmask);
 }
 
 // Forward of a 1x1 convolution whose input is the block output relu(bn(x) + residual) of the bottleneck before it,
@@ -1686,10 +1656,10 @@ int plx_gemm_nt_bnapply(const void* x, const void* res, const float* sb, const f
     const BnApply ba{(const __bf16*)res, sb, rsb, (__bf16*)out, mask};
     hipStream_t s = (hipStream_t)stream;
     if (N % 128 == 0)
-        return rsb != nullptr ? launch_nt_bnapply<128, 128, 2, 2, 2>(x, ba, W, C, M, N, K, ldb, ldc, stats, s)
-                              : launch_nt_bnapply<128, 128, 2, 2, 1>(x, ba, W, C, M, N, K, ldb, ldc, stats, s);
-    return rsb != nullptr ? launch_nt_bnapply<256, 64, 4, 1, 2>(x, ba, W, C, M, N, K, ldb, ldc, stats, s)
-                          : launch_nt_bnapply<256, 64, 4, 1, 1>(x, ba, W, C, M, N, K, ldb, ldc, stats, s);
+        return rsb != nullptr ? launch_nt_prod<128, 128, 2, 2, false, 2>(x, {}, ba, W, C, M, N, K, ldb, ldc, stats, s)
+                              : launch_nt_prod<128, 128, 2, 2, false, 1>(x, {}, ba, W, C, M, N, K, ldb, ldc, stats, s);
+    return rsb != nullptr ? launch_nt_prod<256, 64, 4, 1, false, 2>(x, {}, ba, W, C, M, N, K, ldb, ldc, stats, s)
+                          : launch_nt_prod<256, 64, 4, 1, false, 1>(x, {}, ba, W, C, M, N, K, ldb, ldc, stats, s);
 }
 
 // diagnostics: K slices (fp32 slabs) the weight-gradient plan of this problem uses (v2: wgrad_kernel's plan)
@@ -1713,20 +1683,13 @@ void plx_set_tn_v2(int on, int lds_kb) {
     if (lds_kb > 0) g_tn2_lds_kb = lds_kb <= 64 ? 64 : 128;
 }
 
-// floats of slab workspace plx_gemm_tn needs for this problem
+// floats of slab workspace plx_gemm_tn needs for this problem: the larger of the v1 and v2 plans (the LDS ring budget
+// changes no plan), so the size holds whatever the test hooks select
 long plx_gemm_tn_workspace(int M, int N1, int N2, int num_cus) {
     if (M <= 0 || N1 % 64 || N2 % 64) return -1;
-    const TnPlan a = tn_plan(M, N1, N2, num_cus);
-    long n = a.slices + (a.groups > 1 ? a.groups : 0);
-    for (int kb = 64; kb <= 128; kb += 64) {  // both v2 ring budgets, whatever the knob
-        const int keep = g_tn2_lds_kb;
-        g_tn2_lds_kb = kb;
-        const TnPlan c = tn2_plan(M, N1, N2, num_cus, v2_cfg(N1, N2));
-        g_tn2_lds_kb = keep;
-        const long nc = c.slices + (c.groups > 1 ? c.groups : 0);
-        if (nc > n) n = nc;
-    }
-    return n * N1 * N2;
+    const long a = plan_slabs(tn_plan(M, N1, N2, num_cus));
+    const long b = plan_slabs(tn2_plan(M, N1, N2, num_cus, v2_cfg(N1, N2)));
+    return (a > b ? a : b) * N1 * N2;
 }
 
 }  // extern "C"
@@ -1734,7 +1697,7 @@ long plx_gemm_tn_workspace(int M, int N1, int N2, int num_cus) {
 namespace {
 template <int CONV>
 int run_tn(const void* A, const void* B, float* C, float* ws, int M, int N1, int N2, int lda, int ldb, int ldc,
-           const void* zero, int num_cus, int accumulate, hipStream_t s, ConvGeom geo, int bpc = 0) {
+           int num_cus, int accumulate, hipStream_t s, ConvGeom geo, int bpc = 0) {
     // 2: v2 for the gathered (KxK / strided) ones; the stem (CONV 2) by its own knob g_tn2_stem
     const V2Cfg cfg = v2_cfg(N1, N2);
     // the 6-wave configuration (the C = 64 3x3 layers: N2 = 9 x 64) is slower than v1 in isolation (144 vs 127 us)
@@ -1753,13 +1716,13 @@ int run_tn(const void* A, const void* B, float* C, float* ws, int M, int N1, int
     if (v2)
         rc = dispatch_tn2<CONV>(cfg, A, B, ws, M, N1, N2, lda, ldb, plan, s, geo);
     else if (N1 % 128 == 0 && N2 % 128 == 0)
-        rc = launch_tn<128, 128, 2, 2, CONV>(A, B, ws, M, N1, N2, lda, ldb, plan, zero, s, geo);
+        rc = launch_tn<128, 128, 2, 2, CONV>(A, B, ws, M, N1, N2, lda, ldb, plan, s, geo);
     else if (N1 % 128 == 0)
-        rc = launch_tn<128, 64, 4, 1, CONV>(A, B, ws, M, N1, N2, lda, ldb, plan, zero, s, geo);
+        rc = launch_tn<128, 64, 4, 1, CONV>(A, B, ws, M, N1, N2, lda, ldb, plan, s, geo);
     else if (N2 % 128 == 0)
-        rc = launch_tn<64, 128, 1, 4, CONV>(A, B, ws, M, N1, N2, lda, ldb, plan, zero, s, geo);
+        rc = launch_tn<64, 128, 1, 4, CONV>(A, B, ws, M, N1, N2, lda, ldb, plan, s, geo);
     else
-        rc = launch_tn<64, 64, 2, 2, CONV>(A, B, ws, M, N1, N2, lda, ldb, plan, zero, s, geo);
+        rc = launch_tn<64, 64, 2, 2, CONV>(A, B, ws, M, N1, N2, lda, ldb, plan, s, geo);
     if (rc) return rc;
     const long plane = (long)N1 * N2;
     const float* slabs = ws;
@@ -1839,9 +1802,9 @@ extern "C" {
 
 // C[N1][N2] (ldc, fp32) = (accumulate ? C : 0) + A^T B over M rows; ws holds plx_gemm_tn_workspace floats
 int plx_gemm_tn(const void* A, const void* B, float* C, float* ws, int M, int N1, int N2, int lda, int ldb, int ldc,
-                const void* zero, int num_cus, int accumulate, void* stream) {
+                int num_cus, int accumulate, void* stream) {
     if (M <= 0 || N1 % 64 || N2 % 64 || lda % 8 || ldb % 8 || ldc % 4) return -1;
-    return run_tn<false>(A, B, C, ws, M, N1, N2, lda, ldb, ldc, zero, num_cus, accumulate, (hipStream_t)stream, {});
+    return run_tn<false>(A, B, C, ws, M, N1, N2, lda, ldb, ldc, num_cus, accumulate, (hipStream_t)stream, {});
 }
 
 // ---- KxK (K = 1 or 3, pad = K/2) convolutions with stride 1 or 2 on NHWC bf16 (Cin, Cout multiples of 64)
@@ -1864,26 +1827,24 @@ inline ConvGeom fwd_geom(int H, int W, int C, int K, int S) {
 }
 
 template <int BM_, int BN_, int WGM_, int WGN_, int NBUF_>
-int nt_conv(const void* A, const void* B, void* C, int M, int N, const ConvGeom& g, int ldb, int ldc,
-            const void* zero, float* stats, hipStream_t s, const void* D, const BnBwd& bnr) {
-    return launch_nt<BM_, BN_, WGM_, WGN_, true, NBUF_>(A, B, C, M, N, g.ntaps * g.C, g.C, ldb, ldc, zero, stats, s, g, D,
-                                                 D != nullptr ? ldc : 0, bnr);
+int nt_conv(const void* A, const void* B, void* C, int M, int N, const ConvGeom& g, int ldb, int ldc, float* stats,
+            hipStream_t s, const void* D, const BnBwd& bnr) {
+    return launch_nt<BM_, BN_, WGM_, WGN_, true, NBUF_>(A, B, C, M, N, g.ntaps * g.C, g.C, ldb, ldc, stats, s, g, D,
+                                                        D != nullptr ? ldc : 0, bnr);
 }
 
-inline int nt_rows_per_block(int N) { return N % 128 == 0 ? 128 : 256; }
-
 int nt_conv_any(const void* A, const void* B, void* C, int M, int N, const ConvGeom& g_in, int ldb, int ldc,
-                const void* zero, float* stats, hipStream_t s, const void* D = nullptr, const BnBwd& bnr = {}) {
+                float* stats, hipStream_t s, const void* D = nullptr, const BnBwd& bnr = {}) {
     ConvGeom g = g_in;
     g.tap_inner = 1;  // tap-inner reduction order (ConvGeom::tap_inner; tap-major measured slower)
     const int K = g.ntaps * g.C;
     if (N % 128 == 0)
         return nt_single(true, K, ((M + 127) / 128) * (N / 128))
-                   ? nt_conv<128, 128, 2, 2, 1>(A, B, C, M, N, g, ldb, ldc, zero, stats, s, D, bnr)
-                   : nt_conv<128, 128, 2, 2, 2>(A, B, C, M, N, g, ldb, ldc, zero, stats, s, D, bnr);
+                   ? nt_conv<128, 128, 2, 2, 1>(A, B, C, M, N, g, ldb, ldc, stats, s, D, bnr)
+                   : nt_conv<128, 128, 2, 2, 2>(A, B, C, M, N, g, ldb, ldc, stats, s, D, bnr);
     return nt_single(true, K, ((M + 255) / 256) * (N / 64))
-               ? nt_conv<256, 64, 4, 1, 1>(A, B, C, M, N, g, ldb, ldc, zero, stats, s, D, bnr)
-               : nt_conv<256, 64, 4, 1, 2>(A, B, C, M, N, g, ldb, ldc, zero, stats, s, D, bnr);
+               ? nt_conv<256, 64, 4, 1, 1>(A, B, C, M, N, g, ldb, ldc, stats, s, D, bnr)
+               : nt_conv<256, 64, 4, 1, 2>(A, B, C, M, N, g, ldb, ldc, stats, s, D, bnr);
 }
 
 // the GEMMs of a data gradient: (row grid geometry, ntaps) per launch; S == 2 gives one per parity class
@@ -1931,10 +1892,10 @@ extern "C" {
 
 // y[Nb*Ho*Wo][Cout] = conv(x[Nb*H*W][Cin], Wf[Cout][K*K][Cin]); stats as in plx_gemm_nt
 int plx_conv_fwd(const void* x, const void* wf, void* y, int Nb, int H, int W, int Cin, int Cout, int K, int S,
-                 const void* zero, float* stats, void* stream) {
+                 float* stats, void* stream) {
     if (Nb <= 0 || Cin % 64 || Cout % 64 || (K != 1 && K != 3) || (S != 1 && S != 2)) return -1;
     const ConvGeom g = fwd_geom(H, W, Cin, K, S);
-    return nt_conv_any(x, wf, y, Nb * g.Hr * g.Wr, Cout, g, K * K * Cin, Cout, zero, stats, (hipStream_t)stream);
+    return nt_conv_any(x, wf, y, Nb * g.Hr * g.Wr, Cout, g, K * K * Cin, Cout, stats, (hipStream_t)stream);
 }
 
 // dx[Nb*H*W][Cin] = conv^T(dy[Nb*Ho*Wo][Cout], Wd[Cin][K*K][Cout]) (+ D, bf16 [Nb*H*W][Cin], may alias dx).
@@ -1942,16 +1903,16 @@ int plx_conv_fwd(const void* x, const void* wf, void* y, int Nb, int H, int W, i
 // other rows then keep D).  bnr (nullable): fused BatchNorm-backward partials of dx, one block row per GEMM
 // block over all launches (plx_conv_dgrad_blocks of them); only valid when every pixel is written (not S2/K1).
 int plx_conv_dgrad(const void* dy, const void* wd, void* dx, int Nb, int H, int W, int Cin, int Cout, int K, int S,
-                   const void* zero, const void* D, const BnBwd* bnr, void* stream) {
+                   const void* D, const BnBwd* bnr, void* stream) {
     if (Nb <= 0 || Cin % 64 || Cout % 64 || (K != 1 && K != 3) || (S != 1 && S != 2)) return -1;
     // a strided 1x1 writes the even-even pixels only: its partials can only continue a buffer whose other rows
     // (blk_off before it) cover the rest (BnBwd::skip_w)
     if (bnr != nullptr && (S == 2 && K == 1) && bnr->blk_off == 0) return -1;
     hipStream_t st = (hipStream_t)stream;
     BnBwd b = bnr != nullptr ? *bnr : BnBwd{};
-    const int rpb = nt_rows_per_block(Cin);
+    const int rpb = plx_gemm_nt_rows_per_block(Cin);
     return for_each_dgrad_gemm(Nb, H, W, Cin, Cout, K, S, [&](const ConvGeom& g, int M) {
-        const int rc = nt_conv_any(dy, wd, dx, M, Cin, g, K * K * Cout, Cin, zero, nullptr, st, D, b);
+        const int rc = nt_conv_any(dy, wd, dx, M, Cin, g, K * K * Cout, Cin, nullptr, st, D, b);
         b.blk_off += (M + rpb - 1) / rpb;
         return rc;
     });
@@ -1960,7 +1921,7 @@ int plx_conv_dgrad(const void* dy, const void* wd, void* dx, int Nb, int H, int 
 // number of BatchNorm-partial block rows plx_conv_dgrad writes (part_ld for its bnr)
 int plx_conv_dgrad_blocks(int Nb, int H, int W, int Cin, int Cout, int K, int S) {
     int total = 0;
-    const int rpb = nt_rows_per_block(Cin);
+    const int rpb = plx_gemm_nt_rows_per_block(Cin);
     const int rc = for_each_dgrad_gemm(Nb, H, W, Cin, Cout, K, S, [&](const ConvGeom&, int M) {
         total += (M + rpb - 1) / rpb;
         return 0;
@@ -1974,11 +1935,11 @@ long plx_conv_wgrad_workspace(int Nb, int H, int W, int Cin, int Cout, int K, in
 
 // dW[co][tap][ci] (fp32, (+)=) = sum over output pixels m of dy[m][co] * x[gather_tap(m)][ci]
 int plx_conv_wgrad(const void* dy, const void* x, float* dw, float* ws, int Nb, int H, int W, int Cin, int Cout, int K,
-                   int S, const void* zero, int num_cus, int accumulate, void* stream) {
+                   int S, int num_cus, int accumulate, void* stream) {
     if (Nb <= 0 || Cin % 64 || Cout % 64 || (K != 1 && K != 3) || (S != 1 && S != 2)) return -1;
     const ConvGeom g = fwd_geom(H, W, Cin, K, S);
     const int M = Nb * g.Hr * g.Wr;
-    return run_tn<true>(dy, x, dw, ws, M, Cout, K * K * Cin, Cout, Cin, K * K * Cin, zero, num_cus, accumulate,
+    return run_tn<true>(dy, x, dw, ws, M, Cout, K * K * Cin, Cout, Cin, K * K * Cin, num_cus, accumulate,
                         (hipStream_t)stream, g);
 }
 
@@ -2072,12 +2033,23 @@ constexpr int kStemWgradBpc = 4;  // blocks per CU for the stem's weight gradien
 
 // slab planes (slices + reducer groups) of the stem's weight gradient under either plan
 static long stem_slabs(int M, int num_cus) {
-    const TnPlan p = tn_plan(M, 64, 256, num_cus, kStemWgradBpc);
-    const TnPlan q = tn2_plan(M, 64, 256, num_cus, v2_cfg(64, 256));
-    const TnPlan r = tn2_plan(M, 64, 256, num_cus, v2_cfg(64, 256), kStemV2Bpc);
-    const long a = p.slices + (p.groups > 1 ? p.groups : 0), b = q.slices + (q.groups > 1 ? q.groups : 0);
-    const long c = r.slices + (r.groups > 1 ? r.groups : 0);
+    const long a = plan_slabs(tn_plan(M, 64, 256, num_cus, kStemWgradBpc));
+    const long b = plan_slabs(tn2_plan(M, 64, 256, num_cus, v2_cfg(64, 256)));
+    const long c = plan_slabs(tn2_plan(M, 64, 256, num_cus, v2_cfg(64, 256), kStemV2Bpc));
     return a > b ? (a > c ? a : c) : (b > c ? b : c);
+}
+
+// gather geometry of the stem over the packed input: H x W/2 super-pixels, row grid = the output pixels
+// ((H + 2*3 - 7) / 2 + 1 rows)
+static ConvGeom stem_geom(int H, int W) {
+    ConvGeom g{};
+    g.H = H;
+    g.W = W / 2;
+    g.Hr = (H - 1) / 2 + 1;
+    g.Wr = (W - 1) / 2 + 1;
+    g.mWr = div_magic(g.Wr);
+    g.mHr = div_magic(g.Hr);
+    return g;
 }
 
 // floats of workspace plx_stem_conv_wgrad needs: the slab reduction's (as plx_gemm_tn_workspace) + dW packed [64][256]
@@ -2090,44 +2062,28 @@ long plx_stem_conv_wgrad_workspace(int N, int H, int W, int num_cus) {
 // [N][Ho][Wo][64]) and the packed input xp: a TN GEMM over the output pixels gathering the super-pixel window
 // (stage_rows GATHER 2), then unpacked from the [64][28 x 8] chunk layout
 int plx_stem_conv_wgrad(const void* dy, const void* xp, float* dw, long s_co, long s_ci, long s_kh, long s_kw,
-                        float* ws, int N, int H, int W, const void* zero, int num_cus, int accumulate, void* stream) {
+                        float* ws, int N, int H, int W, int num_cus, int accumulate, void* stream) {
     if (N <= 0 || H <= 0 || W <= 0 || (W & 1)) return -1;
-    ConvGeom g{};
-    g.H = H;
-    g.W = W / 2;
-    g.Hr = (H - 1) / 2 + 1;
-    g.Wr = (W - 1) / 2 + 1;
-    g.mWr = div_magic(g.Wr);
-    g.mHr = div_magic(g.Hr);
+    const ConvGeom g = stem_geom(H, W);
     const int M = N * g.Hr * g.Wr;
     float* packed = ws + stem_slabs(M, num_cus) * 64 * 256;
     hipStream_t s = (hipStream_t)stream;
-    const int rc = run_tn<2>(dy, xp, packed, ws, M, 64, 256, 64, 8, 256, zero, num_cus, 0, s, g, kStemWgradBpc);
+    const int rc = run_tn<2>(dy, xp, packed, ws, M, 64, 256, 64, 8, 256, num_cus, 0, s, g, kStemWgradBpc);
     if (rc) return rc;
     hipLaunchKernelGGL(stem_unpack_wgrad_kernel, dim3((64 * 147 + 255) / 256), dim3(256), 0, s, packed, dw, s_co, s_ci,
                        s_kh, s_kw, accumulate);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
-// rows of plx_stem_conv_fwd's channel-stat partials: stats is fp32 [2][ceil(M / 256)][64], M = N * Ho * Wo
-int plx_stem_conv_rows_per_block() { return 256; }
-
 // y[N*Ho*Wo][64] (NHWC bf16) = conv7x7/s2/p3(x) from the packed input xp (plx_stem_pack_input) and weights wp
-// (plx_stem_pack_weight); stats (nullable) as plx_gemm_nt's
-int plx_stem_conv_fwd(const void* xp, const void* wp, void* y, int N, int H, int W, const void* zero, float* stats,
-                      void* stream) {
+// (plx_stem_pack_weight); stats (nullable) as plx_gemm_nt's: fp32 [2][ceil(M / 256)][64], M = N * Ho * Wo
+int plx_stem_conv_fwd(const void* xp, const void* wp, void* y, int N, int H, int W, float* stats, void* stream) {
     if (N <= 0 || H <= 0 || W <= 0 || (W & 1)) return -1;
-    ConvGeom g{};
-    g.H = H;
-    g.W = W / 2;                                    // super-pixel columns
-    g.Hr = (H - 1) / 2 + 1;                         // (H + 2*3 - 7) / 2 + 1
-    g.Wr = (W - 1) / 2 + 1;
-    g.mWr = div_magic(g.Wr);
-    g.mHr = div_magic(g.Hr);
+    const ConvGeom g = stem_geom(H, W);
     const int M = N * g.Hr * g.Wr;
     return nt_single(true, 256, (M + 255) / 256)
-               ? launch_nt<256, 64, 4, 1, 2, 1>(xp, wp, y, M, 64, 256, 8, 256, 64, zero, stats, (hipStream_t)stream, g)
-               : launch_nt<256, 64, 4, 1, 2, 2>(xp, wp, y, M, 64, 256, 8, 256, 64, zero, stats, (hipStream_t)stream, g);
+               ? launch_nt<256, 64, 4, 1, 2, 1>(xp, wp, y, M, 64, 256, 8, 256, 64, stats, (hipStream_t)stream, g)
+               : launch_nt<256, 64, 4, 1, 2, 2>(xp, wp, y, M, 64, 256, 8, 256, 64, stats, (hipStream_t)stream, g);
 }
 
 }  // extern "C"

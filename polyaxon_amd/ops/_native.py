@@ -271,7 +271,7 @@ SIGNATURES: Dict[str, Dict[str, list]] = {
                           _P],
     },
     "plx_conv": {
-        "plx_gemm_nt": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P],
+        "plx_gemm_nt": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P],
         "plx_gemm_nt_bndx": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P],
         "plx_gemm_nt_bnapply": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P],
         "plx_gemm_nt_rows_per_block": [_I],
@@ -281,21 +281,20 @@ SIGNATURES: Dict[str, Dict[str, list]] = {
         "plx_set_tn2_c64": [_I],
         "plx_set_tn_atomic": [_I],
         "plx_tn_plan_slices": [_I, _I, _I, _I, _I],
-        "plx_gemm_tn": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P],
+        "plx_gemm_tn": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
         "plx_weight_prep": [_P, _P, _P, _I, _I, _P],
         "plx_weight_prepk": [_P, _L, _L, _L, _L, _P, _P, _I, _I, _I, _P],
         "plx_weight_prep_all": [_P, _P, _P, _P, _I, _I, _P],
         "plx_stem_pack_input": [_P, _P, _I, _I, _I, _P],
         "plx_stem_pack_weight": [_P, _L, _L, _L, _L, _P, _I, _P],
-        "plx_stem_conv_rows_per_block": [],
-        "plx_stem_conv_fwd": [_P, _P, _P, _I, _I, _I, _P, _P, _P],
+        "plx_stem_conv_fwd": [_P, _P, _P, _I, _I, _I, _P, _P],
         "plx_stem_conv_wgrad_workspace": [_I, _I, _I, _I],
-        "plx_stem_conv_wgrad": [_P, _P, _P, _L, _L, _L, _L, _P, _I, _I, _I, _P, _I, _I, _P],
-        "plx_conv_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P],
-        "plx_conv_dgrad": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P],
+        "plx_stem_conv_wgrad": [_P, _P, _P, _L, _L, _L, _L, _P, _I, _I, _I, _I, _I, _P],
+        "plx_conv_fwd": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P],
+        "plx_conv_dgrad": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P],
         "plx_conv_dgrad_blocks": [_I, _I, _I, _I, _I, _I, _I],
         "plx_conv_wgrad_workspace": [_I, _I, _I, _I, _I, _I, _I, _I],
-        "plx_conv_wgrad": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P],
+        "plx_conv_wgrad": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     },
     "plx_lm": {
         "plx_qkv_rope_fwd": [_P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _P],

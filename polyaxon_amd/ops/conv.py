@@ -3,8 +3,8 @@
 Every ResNet-50 convolution except the 3-channel stem goes through here or through the dense 1x1 path of
 :mod:`polyaxon_amd.ops.conv1x1`.  Each pass reuses the GEMM kernels with a gathered operand: the reduction
 index is (tap, channel), and the operand row for a tap is the pixel shifted by that tap, read straight from
-the NHWC activation by the per-lane global->LDS copy (out-of-image taps read a zero page = the padding).  No
-im2col buffer is ever materialised.
+the NHWC activation by the per-lane global->LDS copy (out-of-image taps get an out-of-range buffer offset, which
+reads zeros = the padding).  No im2col buffer is ever materialised.
 
 * forward      ``y[m][co] = Σ_tap,ci x[S·m + tap - p][ci] · W[co][tap][ci]``         (+ BN channel stats)
 * data grad    stride 1: the same gather with flipped taps over dy; stride 2: one GEMM per (ih, iw) parity
@@ -23,7 +23,7 @@ import torch.nn.functional as F
 import ctypes
 
 from polyaxon_amd.ops import _native, side_stream, wcache
-from polyaxon_amd.ops.conv1x1 import (GradMailbox, _bf16_context, _num_cus, _stream, _zero_page, bn_link_of, nt_stats_rows,
+from polyaxon_amd.ops.conv1x1 import (GradMailbox, _bf16_context, _num_cus, _stream, bn_link_of, nt_stats_rows,
                                       unpack_relu_mask)
 from polyaxon_amd.ops.flat import direct_grad
 
@@ -57,8 +57,7 @@ class _ConvK(torch.autograd.Function):
         wf, wd = wcache.lookup(weight) or weight_prep_k(weight)
         y = torch.empty((n, cout, ho, wo), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
         rc = lib.plx_conv_fwd(x.data_ptr(), wf.data_ptr(), y.data_ptr(), n, h, w, cin, cout, k, stride,
-                              _zero_page(x.device).data_ptr(), stats.data_ptr() if stats is not None else None,
-                              _stream())
+                              stats.data_ptr() if stats is not None else None, _stream())
         _native.check(rc, "plx_conv_fwd")
         ctx.save_for_backward(x, wd)
         ctx.wshape = weight.shape
@@ -79,7 +78,6 @@ class _ConvK(torch.autograd.Function):
         cout, k = ctx.wshape[0], ctx.wshape[2]
         s = ctx.stride
         dy = dy.to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
-        zero = _zero_page(x.device).data_ptr()
         dx = dw = None
         extra, extra_mask = ctx.box.take() if ctx.box is not None else (None, None)
         if extra is not None and extra_mask is not None:
@@ -102,7 +100,7 @@ class _ConvK(torch.autograd.Function):
             elif ctx.link is not None and (ctx.box is None or extra is not None):
                 nblk = _native.size("plx_conv", "plx_conv_dgrad_blocks", n, h, w, cin, cout, k, s)
                 bnr = ctx.link.request(nblk)
-            rc = lib.plx_conv_dgrad(dy.data_ptr(), wd.data_ptr(), dx.data_ptr(), n, h, w, cin, cout, k, s, zero,
+            rc = lib.plx_conv_dgrad(dy.data_ptr(), wd.data_ptr(), dx.data_ptr(), n, h, w, cin, cout, k, s,
                                     add.data_ptr() if add is not None else None,
                                     ctypes.addressof(bnr) if bnr is not None else None, _stream())
             _native.check(rc, "plx_conv_dgrad")
@@ -115,7 +113,7 @@ class _ConvK(torch.autograd.Function):
                 ws = torch.empty(_native.size("plx_conv", "plx_conv_wgrad_workspace", n, h, w, cin, cout, k, s, cus),
                                  dtype=torch.float32, device=x.device)
                 rc = lib.plx_conv_wgrad(dy.data_ptr(), x.data_ptr(), g.data_ptr(), ws.data_ptr(), n, h, w, cin, cout,
-                                        k, s, zero, cus, int(direct), _stream())
+                                        k, s, cus, int(direct), _stream())
                 _native.check(rc, "plx_conv_wgrad")
             if direct:  # only the optimizer reads the flat slot: overlap with the data-gradient chain
                 side_stream.run(wgrad, (dy, x), x.device)

@@ -25,7 +25,6 @@ import torch.nn.functional as F
 from polyaxon_amd.ops import _native, side_stream, wcache
 from polyaxon_amd.ops.flat import direct_grad
 
-_ZERO: Dict[int, torch.Tensor] = {}
 _CUS: Dict[int, int] = {}
 
 # A/B knob, read once at load: 1 = a BatchNorm backward hands its dx pass to the data-gradient GEMM of the 1x1
@@ -56,11 +55,6 @@ def bn_apply_fused() -> bool:
     return _BN_APPLY_FUSED
 
 
-def _zero_page(dev: torch.device) -> torch.Tensor:
-    idx = dev.index if dev.index is not None else torch.cuda.current_device()
-    return _native.cached(_ZERO, idx, lambda: torch.zeros(256, dtype=torch.bfloat16, device=dev))
-
-
 def _num_cus(dev: torch.device) -> int:
     idx = dev.index if dev.index is not None else torch.cuda.current_device()
     if idx not in _CUS:
@@ -77,6 +71,21 @@ def nt_stats_rows(n: int) -> int:
     return _native.size("plx_conv", "plx_gemm_nt_rows_per_block", n)
 
 
+def _check_stats(stats, m: int, n: int) -> None:
+    """``stats`` (or None) can hold the channel-stats partials of an M x N output, fp32 [2][nblk][N]."""
+    if stats is not None:
+        nblk = -(-m // nt_stats_rows(n))
+        assert stats.dtype == torch.float32 and stats.is_contiguous() and stats.numel() >= 2 * nblk * n
+
+
+def _check_add(add, add_mask, m: int, n: int) -> None:
+    """``add`` (or None) is a bf16 [M][N] epilogue addend; ``add_mask`` (or None) its 1-bit mask over dense rows."""
+    if add is not None:
+        assert add.shape == (m, n) and add.stride(1) == 1 and add.dtype == torch.bfloat16 and add.data_ptr() % 16 == 0
+    if add_mask is not None:
+        assert add is not None and add.stride(0) == n and add_mask.dtype == torch.uint8 and add_mask.numel() == m * n // 8
+
+
 def gemm_nt(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor = None, stats: torch.Tensor = None,
             add: torch.Tensor = None, bnr: "_native.GemmBnBwdArgs" = None,
             add_mask: torch.Tensor = None) -> torch.Tensor:
@@ -91,15 +100,10 @@ def gemm_nt(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor = None, stats: t
         out = torch.empty(m, n, dtype=torch.bfloat16, device=a.device)
     assert a.stride(1) == 1 and b.stride(1) == 1 and out.stride(1) == 1 and b.shape[1] == k
     assert a.data_ptr() % 16 == 0 and b.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0
-    if stats is not None:
-        nblk = -(-m // nt_stats_rows(n))
-        assert stats.dtype == torch.float32 and stats.is_contiguous() and stats.numel() >= 2 * nblk * n
-    if add is not None:
-        assert add.shape == (m, n) and add.stride(1) == 1 and add.dtype == torch.bfloat16 and add.data_ptr() % 16 == 0
-    if add_mask is not None:
-        assert add is not None and add.stride(0) == n and add_mask.dtype == torch.uint8 and add_mask.numel() == m * n // 8
+    _check_stats(stats, m, n)
+    _check_add(add, add_mask, m, n)
     rc = _native.lib("plx_conv").plx_gemm_nt(a.data_ptr(), b.data_ptr(), out.data_ptr(), m, n, k, a.stride(0),
-                                             b.stride(0), out.stride(0), _zero_page(a.device).data_ptr(),
+                                             b.stride(0), out.stride(0),
                                              stats.data_ptr() if stats is not None else None,
                                              add.data_ptr() if add is not None else None,
                                              add.stride(0) if add is not None else 0,
@@ -129,10 +133,7 @@ def gemm_nt_bndx(g: torch.Tensor, x: torch.Tensor, mask: torch.Tensor, coef: tor
     assert coef.dtype == torch.float32 and coef.is_contiguous() and coef.numel() == 3 * k
     if mask is not None:
         assert mask.dtype == torch.uint8 and mask.numel() == m * k // 8
-    if add is not None:
-        assert add.shape == (m, n) and add.stride(1) == 1 and add.dtype == torch.bfloat16 and add.data_ptr() % 16 == 0
-    if add_mask is not None:
-        assert add is not None and add.stride(0) == n and add_mask.dtype == torch.uint8 and add_mask.numel() == m * n // 8
+    _check_add(add, add_mask, m, n)
     rc = _native.lib("plx_conv").plx_gemm_nt_bndx(g.data_ptr(), x.data_ptr(),
                                                   mask.data_ptr() if mask is not None else None, coef.data_ptr(),
                                                   dy.data_ptr(), b.data_ptr(), out.data_ptr(), m, n, k, b.stride(0),
@@ -165,9 +166,7 @@ def gemm_nt_bnapply(x: torch.Tensor, res: torch.Tensor, sb: torch.Tensor, rsb, o
         assert c is None or (c.dtype == torch.float32 and c.is_contiguous() and c.numel() == 2 * k
                              and c.data_ptr() % 16 == 0)
     assert sb is not None
-    if stats is not None:
-        nblk = -(-m // nt_stats_rows(n))
-        assert stats.dtype == torch.float32 and stats.is_contiguous() and stats.numel() >= 2 * nblk * n
+    _check_stats(stats, m, n)
     rc = _native.lib("plx_conv").plx_gemm_nt_bnapply(x.data_ptr(), res.data_ptr(), sb.data_ptr(),
                                                      rsb.data_ptr() if rsb is not None else None, out_a.data_ptr(),
                                                      mask.data_ptr(), b.data_ptr(), out.data_ptr(), m, n, k,
@@ -191,8 +190,7 @@ def gemm_tn(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor = None, accumula
     ws = torch.empty(_native.size("plx_conv", "plx_gemm_tn_workspace", m, n1, n2, cus), dtype=torch.float32,
                      device=a.device)
     rc = lib.plx_gemm_tn(a.data_ptr(), b.data_ptr(), out.data_ptr(), ws.data_ptr(), m, n1, n2, a.stride(0),
-                         b.stride(0), out.stride(0), _zero_page(a.device).data_ptr(), cus, int(accumulate),
-                         _stream())
+                         b.stride(0), out.stride(0), cus, int(accumulate), _stream())
     _native.check(rc, "plx_gemm_tn")
     return out
 

@@ -19,6 +19,7 @@ import torch
 
 from polyaxon_amd.ops import _native
 from polyaxon_amd.ops.bn_fused import _cl, _counters, _stream
+from polyaxon_amd.ops.conv1x1 import _bf16_context, _num_cus
 from polyaxon_amd.ops.flat import direct_grad
 
 
@@ -119,9 +120,7 @@ class _StemConv(torch.autograd.Function):
                       "plx_stem_pack_weight")
         oh, ow = (h - 1) // 2 + 1, (w - 1) // 2 + 1
         y = torch.empty((n, cout, oh, ow), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
-        from polyaxon_amd.ops.conv1x1 import _zero_page
         rc = conv.plx_stem_conv_fwd(xp.data_ptr(), wp.data_ptr(), y.data_ptr(), n, h, w,
-                                    _zero_page(x.device).data_ptr(),
                                     stats.data_ptr() if stats is not None else None, st)
         _native.check(rc, "plx_stem_conv_fwd")
         ctx.save_for_backward(xp, weight)
@@ -139,22 +138,18 @@ class _StemConv(torch.autograd.Function):
         conv = _native.lib("plx_conv")
         n, h, w = ctx.shape
         dy = _cl(dy.to(torch.bfloat16))
-        from polyaxon_amd.ops.conv1x1 import _num_cus, _zero_page
         cus = _num_cus(dy.device)
         ws = torch.empty(int(conv.plx_stem_conv_wgrad_workspace(n, h, w, cus)), dtype=torch.float32, device=dy.device)
         slot = direct_grad(weight)
         out = slot if slot is not None else torch.empty_like(weight, dtype=torch.float32)
         st_ = out.stride()
         rc = conv.plx_stem_conv_wgrad(dy.data_ptr(), xp.data_ptr(), out.data_ptr(), st_[0], st_[1], st_[2], st_[3],
-                                      ws.data_ptr(), n, h, w, _zero_page(dy.device).data_ptr(), cus,
-                                      int(slot is not None), _stream())
+                                      ws.data_ptr(), n, h, w, cus, int(slot is not None), _stream())
         _native.check(rc, "plx_stem_conv_wgrad")
         return None, (None if slot is not None else out.to(weight.dtype)), None
 
 
 def stem_conv_supported(x: torch.Tensor, conv) -> bool:
-    from polyaxon_amd.ops.conv1x1 import _bf16_context
-
     return (x.is_cuda and x.dim() == 4 and x.shape[1] == 3 and _bf16_context(x) and conv.out_channels == 64
             and conv.kernel_size == (7, 7) and conv.stride == (2, 2) and conv.padding == (3, 3)
             and conv.groups == 1 and conv.bias is None and x.shape[3] % 2 == 0 and x.numel() > 0)

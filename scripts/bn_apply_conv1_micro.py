@@ -18,7 +18,7 @@ import torch
 sys.path.insert(0, __import__("os").path.dirname(__import__("os").path.dirname(__import__("os").path.abspath(__file__))))
 
 from polyaxon_amd.ops import _native  # noqa: E402
-from polyaxon_amd.ops.conv1x1 import _zero_page, nt_stats_rows  # noqa: E402
+from polyaxon_amd.ops.conv1x1 import nt_stats_rows  # noqa: E402
 
 SHAPES = [(802816, 256, 64), (200704, 512, 128), (50176, 1024, 256)]  # (M, K, N) of conv1's forward
 HBM_TBS = 6.3  # achievable HBM bandwidth (measuring-on-mi355x)
@@ -31,7 +31,6 @@ def main():
     dev = torch.device("cuda", 0)
     conv, bn = _native.lib("plx_conv"), _native.lib("plx_bn")
     st = torch.cuda.current_stream().cuda_stream
-    zero = _zero_page(dev).data_ptr()
     f32 = dict(dtype=torch.float32, device=dev)
     for m, k, n in SHAPES:
         act, y = m * k * 2, m * n * 2
@@ -56,7 +55,7 @@ def main():
             rc = bn.plx_bn_apply_res_relu(s["x"].data_ptr(), s["res"].data_ptr(), s["out"].data_ptr(), m, k,
                                           sb.data_ptr(), s["mask"].data_ptr(), rsp, st)
             assert rc == 0
-            rc = conv.plx_gemm_nt(s["out"].data_ptr(), w.data_ptr(), s["y"].data_ptr(), m, n, k, k, k, n, zero,
+            rc = conv.plx_gemm_nt(s["out"].data_ptr(), w.data_ptr(), s["y"].data_ptr(), m, n, k, k, k, n,
                                   stats.data_ptr(), None, 0, None, None, st)
             assert rc == 0
 

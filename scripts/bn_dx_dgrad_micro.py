@@ -21,7 +21,7 @@ sys.path.insert(0, __import__("os").path.dirname(__import__("os").path.dirname(_
 
 from polyaxon_amd.ops import _native  # noqa: E402
 from polyaxon_amd.ops.bn_fused import _counters, bn_backward  # noqa: E402
-from polyaxon_amd.ops.conv1x1 import _zero_page, nt_stats_rows  # noqa: E402
+from polyaxon_amd.ops.conv1x1 import nt_stats_rows  # noqa: E402
 
 SHAPES = [(802816, 256, 64), (200704, 512, 128), (50176, 1024, 256), (12544, 2048, 512)]  # (M, K, N) of conv3's dgrad
 HBM_TBS = 6.3  # achievable HBM bandwidth (measuring-on-mi355x)
@@ -33,7 +33,7 @@ def main():
     dev = torch.device("cuda", 0)
     conv = _native.lib("plx_conv")
     st = torch.cuda.current_stream().cuda_stream
-    zero, cnt = _zero_page(dev).data_ptr(), _counters(dev)
+    cnt = _counters(dev)
     f32 = dict(dtype=torch.float32, device=dev)
     for m, k, n in SHAPES:
         act, out = m * k * 2, m * n * 2
@@ -64,7 +64,7 @@ def main():
             bn_backward(x=s["x"], mask=s["mask"], dy=s["g"], dx=s["dy"], m=m, c=k, gamma=gamma, save_mean=mean,
                         save_invstd=invstd, dgamma=dgb, dbeta=dgb[k:], coef=coef, ext_part=part, ext_nblk=nblk,
                         workspace=l2, relu=True, accumulate=0, counters=cnt, stream=st)
-            rc = conv.plx_gemm_nt(s["dy"].data_ptr(), wt.data_ptr(), s["c"].data_ptr(), m, n, k, k, k, n, zero, None, None,
+            rc = conv.plx_gemm_nt(s["dy"].data_ptr(), wt.data_ptr(), s["c"].data_ptr(), m, n, k, k, k, n, None, None,
                                   0, None, ctypes.addressof(s["bnr"]), st)
             assert rc == 0
 

@@ -13,7 +13,6 @@ sys.path.insert(0, __import__("os").path.dirname(__import__("os").path.dirname(_
 
 from polyaxon_amd.ops import _native  # noqa: E402
 from polyaxon_amd.ops.conv import weight_prep_k  # noqa: E402
-from polyaxon_amd.ops.conv1x1 import _zero_page  # noqa: E402
 
 SHAPES = [(256, 64, 56), (256, 128, 28), (256, 256, 14), (256, 512, 7)]  # (batch, channels in = out, side)
 
@@ -24,7 +23,6 @@ def main():
     dev = torch.device("cuda", 0)
     lib = _native.lib("plx_conv")
     st = torch.cuda.current_stream().cuda_stream
-    zero = _zero_page(dev).data_ptr()
     for n, c, h in SHAPES:
         x = torch.randn(n, h, h, c, device=dev).to(torch.bfloat16)
         w = torch.randn(c, c, 3, 3, device=dev) * 0.05
@@ -35,9 +33,9 @@ def main():
         for p in (["fwd", "dgrad"] if which == "both" else [which]):
             def run():
                 if p == "fwd":
-                    rc = lib.plx_conv_fwd(x.data_ptr(), wf.data_ptr(), y.data_ptr(), n, h, h, c, c, 3, 1, zero, None, st)
+                    rc = lib.plx_conv_fwd(x.data_ptr(), wf.data_ptr(), y.data_ptr(), n, h, h, c, c, 3, 1, None, st)
                 else:
-                    rc = lib.plx_conv_dgrad(y.data_ptr(), wd.data_ptr(), x.data_ptr(), n, h, h, c, c, 3, 1, zero, None,
+                    rc = lib.plx_conv_dgrad(y.data_ptr(), wd.data_ptr(), x.data_ptr(), n, h, h, c, c, 3, 1, None,
                                             None, st)
                 assert rc == 0
             run()

@@ -73,7 +73,7 @@ def main():
 def conv3():
     """3x3 stride-1 convs of ResNet-50: MIOpen vs the implicit-GEMM kernels (kernel time per pass)."""
     from polyaxon_amd.ops import _native
-    from polyaxon_amd.ops.conv1x1 import _num_cus, _stream, _zero_page
+    from polyaxon_amd.ops.conv1x1 import _num_cus, _stream
     from polyaxon_amd.ops.conv import weight_prep_k
 
     lib = _native.lib("plx_conv")
@@ -92,17 +92,16 @@ def conv3():
         wf, wd = weight_prep_k(wt)
         y = torch.empty_like(x)
         dx = torch.empty_like(x)
-        z = _zero_page(dev).data_ptr()
         cus = _num_cus(dev)
         ws = torch.empty(int(lib.plx_conv_wgrad_workspace(n, h, w, c, c, 3, 1, cus)), device=dev)
         dw = torch.empty(c, 9, c, device=dev)
         parts = {
-            "fwd": lambda: lib.plx_conv_fwd(x.data_ptr(), wf.data_ptr(), y.data_ptr(), n, h, w, c, c, 3, 1, z, None,
+            "fwd": lambda: lib.plx_conv_fwd(x.data_ptr(), wf.data_ptr(), y.data_ptr(), n, h, w, c, c, 3, 1, None,
                                             _stream()),
-            "dgrad": lambda: lib.plx_conv_dgrad(g.data_ptr(), wd.data_ptr(), dx.data_ptr(), n, h, w, c, c, 3, 1, z,
-                                                _stream()),
+            "dgrad": lambda: lib.plx_conv_dgrad(g.data_ptr(), wd.data_ptr(), dx.data_ptr(), n, h, w, c, c, 3, 1, None,
+                                                None, _stream()),
             "wgrad": lambda: lib.plx_conv_wgrad(g.data_ptr(), x.data_ptr(), dw.data_ptr(), ws.data_ptr(), n, h, w,
-                                                c, c, 3, 1, z, cus, 0, _stream()),
+                                                c, c, 3, 1, cus, 0, _stream()),
         }
         a = min(timeit(miopen) for _ in range(3))
         pt = {k: min(timeit(f) for _ in range(2)) for k, f in parts.items()}
@@ -117,7 +116,7 @@ def strided():
     MIOpen fwd+bwd vs the implicit-GEMM passes."""
     from polyaxon_amd.ops import _native
     from polyaxon_amd.ops.conv import weight_prep_k
-    from polyaxon_amd.ops.conv1x1 import _num_cus, _stream, _zero_page
+    from polyaxon_amd.ops.conv1x1 import _num_cus, _stream
 
     lib = _native.lib("plx_conv")
     for n, cin, h, w, cout, k in [(256, 128, 56, 56, 128, 3), (256, 256, 28, 28, 256, 3), (256, 512, 14, 14, 512, 3),
@@ -138,17 +137,16 @@ def strided():
         wf, wd = weight_prep_k(wt)
         y = torch.empty(n, cout, ho, wo, device=dev, dtype=torch.bfloat16)
         dx = torch.zeros_like(x)
-        z = _zero_page(dev).data_ptr()
         cus = _num_cus(dev)
         ws = torch.empty(int(lib.plx_conv_wgrad_workspace(n, h, w, cin, cout, k, 2, cus)), device=dev)
         dw = torch.empty(cout, k * k, cin, device=dev)
         parts = {
-            "fwd": lambda: lib.plx_conv_fwd(x.data_ptr(), wf.data_ptr(), y.data_ptr(), n, h, w, cin, cout, k, 2, z,
+            "fwd": lambda: lib.plx_conv_fwd(x.data_ptr(), wf.data_ptr(), y.data_ptr(), n, h, w, cin, cout, k, 2,
                                             None, _stream()),
             "dgrad": lambda: lib.plx_conv_dgrad(g.data_ptr(), wd.data_ptr(), dx.data_ptr(), n, h, w, cin, cout, k, 2,
-                                                z, _stream()),
+                                                None, None, _stream()),
             "wgrad": lambda: lib.plx_conv_wgrad(g.data_ptr(), x.data_ptr(), dw.data_ptr(), ws.data_ptr(), n, h, w,
-                                                cin, cout, k, 2, z, cus, 0, _stream()),
+                                                cin, cout, k, 2, cus, 0, _stream()),
         }
         a = min(timeit(miopen) for _ in range(3))
         pt = {kk: min(timeit(f) for _ in range(2)) for kk, f in parts.items()}

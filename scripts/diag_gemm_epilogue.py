@@ -15,11 +15,10 @@ def main() -> None:
     import torch
 
     from polyaxon_amd.ops import _native
-    from polyaxon_amd.ops.conv1x1 import _zero_page, nt_stats_rows
+    from polyaxon_amd.ops.conv1x1 import nt_stats_rows
 
     conv = _native.lib("plx_conv")
     dev = torch.device("cuda")
-    zero = _zero_page(dev).data_ptr()
     st = torch.cuda.current_stream().cuda_stream
 
     def timeit(fn, reps=20):
@@ -53,7 +52,7 @@ def main() -> None:
                                     nblk, 0)
 
         def run(stats_on=False, add=False, bn=False):
-            return lambda: conv.plx_gemm_nt(a.data_ptr(), b.data_ptr(), c.data_ptr(), m, n, k, k, k, n, zero,
+            return lambda: conv.plx_gemm_nt(a.data_ptr(), b.data_ptr(), c.data_ptr(), m, n, k, k, k, n,
                                             stats.data_ptr() if stats_on else None, d.data_ptr() if add else None,
                                             n if add else 0, None, ctypes.addressof(bnr) if bn else None, st)
         plain = timeit(run())

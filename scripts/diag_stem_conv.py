@@ -35,7 +35,6 @@ def timeit(fn, reps=10):
 
 def main():
     from polyaxon_amd.ops import _native
-    from polyaxon_amd.ops.conv1x1 import _zero_page
     from polyaxon_amd.ops.stem import StemConv
 
     dev = torch.device("cuda")
@@ -51,12 +50,11 @@ def main():
     stats = torch.empty(2 * nblk * 64, dtype=torch.float32, device=dev)
     w = conv.weight.detach()
     st = lambda: torch.cuda.current_stream().cuda_stream  # noqa
-    z = _zero_page(dev).data_ptr()
     res = {
         "miopen_fwd": timeit(lambda: F.conv2d(x, wb, None, 2, 3)),
         "pack_input": timeit(lambda: lib.plx_stem_pack_input(x.data_ptr(), xp.data_ptr(), n, 224, 224, st())),
         "pack_weight": timeit(lambda: lib.plx_stem_pack_weight(w.data_ptr(), *w.stride(), wp.data_ptr(), 64, st())),
-        "stem_gemm": timeit(lambda: lib.plx_stem_conv_fwd(xp.data_ptr(), wp.data_ptr(), y.data_ptr(), n, 224, 224, z,
+        "stem_gemm": timeit(lambda: lib.plx_stem_conv_fwd(xp.data_ptr(), wp.data_ptr(), y.data_ptr(), n, 224, 224,
                                                           stats.data_ptr(), st())),
     }
     dy = torch.randn(n, 64, 112, 112, device=dev).to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
@@ -67,7 +65,7 @@ def main():
     res["miopen_wgrad"] = timeit(lambda: torch.ops.aten.convolution_backward(
         dy, x, wb, None, [2, 2], [3, 3], [1, 1], False, [0, 0], 1, [False, True, False]))
     res["stem_wgrad"] = timeit(lambda: lib.plx_stem_conv_wgrad(dy.data_ptr(), xp.data_ptr(), gw.data_ptr(), *gw.stride(),
-                                                               ws.data_ptr(), n, 224, 224, z, cus, 1, st()))
+                                                               ws.data_ptr(), n, 224, 224, cus, 1, st()))
     for k, v in res.items():
         print(json.dumps({"pass": k, "us": round(v, 1)}))
 

@@ -38,13 +38,12 @@ def main() -> None:
 
     from polyaxon_amd.ops import _native
     from polyaxon_amd.ops.bn_fused import bn_backward, bn_forward
-    from polyaxon_amd.ops.conv1x1 import _num_cus, _zero_page, nt_stats_rows
+    from polyaxon_amd.ops.conv1x1 import _num_cus, nt_stats_rows
 
     dev = torch.device("cuda")
     conv = _native.lib("plx_conv")
     bn = _native.lib("plx_bn")
     cus = _num_cus(dev)
-    zero = _zero_page(dev).data_ptr()
     st = torch.cuda.current_stream().cuda_stream
     cnt = torch.zeros(64, dtype=torch.int32, device=dev)  # BatchNorm reduce + finalize tickets
     cptr = cnt.data_ptr() if a.bn_counters else None
@@ -120,10 +119,10 @@ def main() -> None:
         wt = rnd((cin, k * k * cout))
         if gemm:
             fwd = lambda: conv.plx_gemm_nt(x.data_ptr(), wb.data_ptr(), y.data_ptr(), m_out, cout, cin, cin, cin,  # noqa
-                                           cout, zero, stats.data_ptr(), None, 0, None, None, st)
+                                           cout, stats.data_ptr(), None, 0, None, None, st)
         else:
             fwd = lambda: conv.plx_conv_fwd(x.data_ptr(), wb.data_ptr(), y.data_ptr(), nb, h, w, cin, cout, k, s,  # noqa
-                                            zero, stats.data_ptr(), st)
+                                            stats.data_ptr(), st)
         emit(name, "fwd", count, timeit(fwd), 2.0 * (m_in * cin + m_out * cout) + wbytes + stats.numel() * 4, flops)
         # data gradient
         extra = 0.0
@@ -145,24 +144,24 @@ def main() -> None:
         bp = ctypes.addressof(bnr) if bnr is not None else None
         if gemm:
             dg = lambda: conv.plx_gemm_nt(dy.data_ptr(), wt.data_ptr(), dx.data_ptr(), m_in, cin, cout, cout, cout,  # noqa
-                                          cin, zero, None, add.data_ptr() if add is not None else None,
+                                          cin, None, add.data_ptr() if add is not None else None,
                                           cin if add is not None else 0,
                                           amask.data_ptr() if amask is not None else None, bp, st)
         else:
             target = add if (add is not None and k == 1 and s == 2) else dx  # strided 1x1: in place on the deferred grad
             dg = lambda: conv.plx_conv_dgrad(dy.data_ptr(), wt.data_ptr(), target.data_ptr(), nb, h, w, cin, cout,  # noqa
-                                             k, s, zero, add.data_ptr() if add is not None else None, bp, st)
+                                             k, s, add.data_ptr() if add is not None else None, bp, st)
         emit(name, "dgrad", count, timeit(dg), 2.0 * (m_out * cout + m_in * cin) + wbytes + extra, flops)
         # weight gradient into the fp32 flat slot (+=), slab reduction included
         g = torch.zeros(cout, k * k * cin, **f32)
         if gemm:
             ws = torch.empty(int(conv.plx_gemm_tn_workspace(m_out, cout, cin, cus)), **f32)
             wg = lambda: conv.plx_gemm_tn(dy.data_ptr(), x.data_ptr(), g.data_ptr(), ws.data_ptr(), m_out, cout, cin,  # noqa
-                                          cout, cin, cin, zero, cus, 1, st)
+                                          cout, cin, cin, cus, 1, st)
         else:
             ws = torch.empty(int(conv.plx_conv_wgrad_workspace(nb, h, w, cin, cout, k, s, cus)), **f32)
             wg = lambda: conv.plx_conv_wgrad(dy.data_ptr(), x.data_ptr(), g.data_ptr(), ws.data_ptr(), nb, h, w, cin,  # noqa
-                                             cout, k, s, zero, cus, 1, st)
+                                             cout, k, s, cus, 1, st)
         emit(name, "wgrad", count, timeit(wg), 2.0 * (m_out * cout + m_in * cin) + 8.0 * cout * cin * k * k, flops)
 
     def bn_layer(name, count, m, c, relu, res, partials_bwd):

@@ -9,13 +9,16 @@ same with a 64 KB ring (two blocks per CU, or room for other kernels' blocks bes
 """
 import argparse
 import json
+import os
 import sys
 
-import torch
-import torch.nn.functional as F
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from polyaxon_amd.ops import _native
-from polyaxon_amd.ops.conv1x1 import _num_cus, _zero_page
+import torch  # noqa: E402
+import torch.nn.functional as F  # noqa: E402
+
+from polyaxon_amd.ops import _native  # noqa: E402
+from polyaxon_amd.ops.conv1x1 import _num_cus  # noqa: E402
 
 # (n, cin, h, w, cout, k, s) -- input image h x w; COUNT = how many of each one ResNet-50 step runs
 SHAPES = [(256, 64, 56, 56, 256, 1, 1), (256, 256, 56, 56, 64, 1, 1), (256, 64, 56, 56, 64, 1, 1),
@@ -42,7 +45,6 @@ def main():
     dev = torch.device("cuda", 0)
     lib = _native.lib("plx_conv")
     cus = _num_cus(dev)
-    zero = _zero_page(dev).data_ptr()
     stream = torch.cuda.current_stream().cuda_stream
     idx = [int(i) for i in args.shapes.split(",")] if args.shapes else list(range(len(SHAPES)))
     cases = []
@@ -74,11 +76,11 @@ def main():
 
             def run():
                 _native.check(lib.plx_gemm_tn(dy.data_ptr(), x.data_ptr(), out.data_ptr(), ws.data_ptr(), m, cout, cin,
-                                              cout, cin, cin, zero, cus, 0, stream), "plx_gemm_tn")
+                                              cout, cin, cin, cus, 0, stream), "plx_gemm_tn")
         else:
             def run():
                 _native.check(lib.plx_conv_wgrad(dy.data_ptr(), x.data_ptr(), out.data_ptr(), ws.data_ptr(), n, h, w,
-                                                 cin, cout, k, s, zero, cus, 0, stream), "plx_conv_wgrad")
+                                                 cin, cout, k, s, cus, 0, stream), "plx_conv_wgrad")
         return run
 
     res = {v: {c[0]: [] for c in cases} for v in variants}
