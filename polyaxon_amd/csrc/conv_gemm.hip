@@ -691,9 +691,10 @@ gemm_nt_kernel(const __bf16* __restrict__ A, const __bf16* __restrict__ B, __bf1
             }
         }
         if (d_on) {
-            // C = A.B^T + D (a second gradient into the same tensor, e.g. the residual branch's): added in fp32
-            // and rounded once, instead of a separate bf16 add pass over both tensors.  D is indexed like C, so
-            // D == C (in place) is allowed.
+            // C = A.B^T + D (a second gradient into the same tensor, e.g. the residual branch's) instead of a
+            // separate bf16 add pass over both tensors.  v is the product as tile_to_lds packed it, already rounded to
+            // bf16: D is added to that in fp32 and the sum is rounded again, C = bf16(bf16(A.B^T) + D * mask) -- two
+            // roundings, the result of the separate add pass.  D is indexed like C, so D == C (in place) is allowed.
             uint32_t* pv = (uint32_t*)&v;
             const uint32_t* pd = (const uint32_t*)&dpre[it];
             const uint32_t db = dmask != nullptr ? dmpre[it] : 0xffu;
@@ -1370,6 +1371,13 @@ int launch_nt_prod(const void* A, const BnDx& bd, const BnApply& ba, const void*
 
 inline bool nt_single(bool conv, int K, int nwg) { return nwg >= 768 || (!conv && K == BK); }
 
+// The instantiation an NT GEMM runs, as BM + 1000 * NBUF: the 128x128 tile for N % 128 == 0, else 256x64 (pixels x
+// channels), single- or double-buffered by nt_single over that tile's grid.  conv: the gathered kernels (MODE 1, 2)
+inline int nt_plan(bool conv, int M, int N, int K) {
+    const int bm = N % 128 == 0 ? 128 : 256, bn = N % 128 == 0 ? 128 : 64;
+    return bm + 1000 * (nt_single(conv, K, ((M + bm - 1) / bm) * (N / bn)) ? 1 : 2);
+}
+
 // m-slicing of the weight-gradient GEMM
 struct TnPlan { int kchunk, slices, groups, per_group, blocks, bn1, bn2; };
 
@@ -1605,14 +1613,23 @@ int plx_gemm_nt(const void* A, const void* B, void* C, int M, int N, int K, int 
     if (bnr != nullptr && (ldc != N || bnr->part == nullptr)) return -1;
     const BnBwd b = bnr != nullptr ? *bnr : BnBwd{};
     hipStream_t s = (hipStream_t)stream;
-    if (N % 128 == 0) {
-        const bool one = nt_single(false, K, ((M + 127) / 128) * (N / 128));
-        return one ? launch_nt<128, 128, 2, 2, false, 1>(A, B, C, M, N, K, lda, ldb, ldc, stats, s, {}, D, ldd, b, dmask)
-                   : launch_nt<128, 128, 2, 2>(A, B, C, M, N, K, lda, ldb, ldc, stats, s, {}, D, ldd, b, dmask);
+    switch (nt_plan(false, M, N, K)) {
+        case 1128:
+            return launch_nt<128, 128, 2, 2, false, 1>(A, B, C, M, N, K, lda, ldb, ldc, stats, s, {}, D, ldd, b, dmask);
+        case 2128:
+            return launch_nt<128, 128, 2, 2>(A, B, C, M, N, K, lda, ldb, ldc, stats, s, {}, D, ldd, b, dmask);
+        case 1256:
+            return launch_nt<256, 64, 4, 1, false, 1>(A, B, C, M, N, K, lda, ldb, ldc, stats, s, {}, D, ldd, b, dmask);
+        default:
+            return launch_nt<256, 64, 4, 1>(A, B, C, M, N, K, lda, ldb, ldc, stats, s, {}, D, ldd, b, dmask);
     }
-    const bool one = nt_single(false, K, ((M + 255) / 256) * (N / 64));
-    return one ? launch_nt<256, 64, 4, 1, false, 1>(A, B, C, M, N, K, lda, ldb, ldc, stats, s, {}, D, ldd, b, dmask)
-               : launch_nt<256, 64, 4, 1>(A, B, C, M, N, K, lda, ldb, ldc, stats, s, {}, D, ldd, b, dmask);
+}
+
+// diagnostics: the instantiation plx_gemm_nt (conv == 0) or the implicit-GEMM convolutions and the stem (conv != 0,
+// K = taps * channels) run for an M x N x K problem, as tile height + 1000 * K-stage buffers (1128, 2128, 1256, 2256)
+int plx_gemm_nt_plan(int M, int N, int K, int conv) {
+    if (M <= 0 || N <= 0 || N % 64 || K <= 0 || K % BK) return -1;
+    return nt_plan(conv != 0, M, N, K);
 }
 
 // Data gradient of a 1x1 convolution whose incoming gradient is a BatchNorm backward's dx, produced in the kernel:
@@ -1837,14 +1854,12 @@ int nt_conv_any(const void* A, const void* B, void* C, int M, int N, const ConvG
                 float* stats, hipStream_t s, const void* D = nullptr, const BnBwd& bnr = {}) {
     ConvGeom g = g_in;
     g.tap_inner = 1;  // tap-inner reduction order (ConvGeom::tap_inner; tap-major measured slower)
-    const int K = g.ntaps * g.C;
-    if (N % 128 == 0)
-        return nt_single(true, K, ((M + 127) / 128) * (N / 128))
-                   ? nt_conv<128, 128, 2, 2, 1>(A, B, C, M, N, g, ldb, ldc, stats, s, D, bnr)
-                   : nt_conv<128, 128, 2, 2, 2>(A, B, C, M, N, g, ldb, ldc, stats, s, D, bnr);
-    return nt_single(true, K, ((M + 255) / 256) * (N / 64))
-               ? nt_conv<256, 64, 4, 1, 1>(A, B, C, M, N, g, ldb, ldc, stats, s, D, bnr)
-               : nt_conv<256, 64, 4, 1, 2>(A, B, C, M, N, g, ldb, ldc, stats, s, D, bnr);
+    switch (nt_plan(true, M, N, g.ntaps * g.C)) {
+        case 1128: return nt_conv<128, 128, 2, 2, 1>(A, B, C, M, N, g, ldb, ldc, stats, s, D, bnr);
+        case 2128: return nt_conv<128, 128, 2, 2, 2>(A, B, C, M, N, g, ldb, ldc, stats, s, D, bnr);
+        case 1256: return nt_conv<256, 64, 4, 1, 1>(A, B, C, M, N, g, ldb, ldc, stats, s, D, bnr);
+        default: return nt_conv<256, 64, 4, 1, 2>(A, B, C, M, N, g, ldb, ldc, stats, s, D, bnr);
+    }
 }
 
 // the GEMMs of a data gradient: (row grid geometry, ntaps) per launch; S == 2 gives one per parity class
@@ -2081,7 +2096,7 @@ int plx_stem_conv_fwd(const void* xp, const void* wp, void* y, int N, int H, int
     if (N <= 0 || H <= 0 || W <= 0 || (W & 1)) return -1;
     const ConvGeom g = stem_geom(H, W);
     const int M = N * g.Hr * g.Wr;
-    return nt_single(true, 256, (M + 255) / 256)
+    return nt_plan(true, M, 64, 256) == 1256
                ? launch_nt<256, 64, 4, 1, 2, 1>(xp, wp, y, M, 64, 256, 8, 256, 64, stats, (hipStream_t)stream, g)
                : launch_nt<256, 64, 4, 1, 2, 2>(xp, wp, y, M, 64, 256, 8, 256, 64, stats, (hipStream_t)stream, g);
 }

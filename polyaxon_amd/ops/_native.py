@@ -275,6 +275,7 @@ SIGNATURES: Dict[str, Dict[str, list]] = {
         "plx_gemm_nt_bndx": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P],
         "plx_gemm_nt_bnapply": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P],
         "plx_gemm_nt_rows_per_block": [_I],
+        "plx_gemm_nt_plan": [_I, _I, _I, _I],
         "plx_gemm_tn_workspace": [_I, _I, _I, _I],
         "plx_set_tn_v2": [_I, _I],
         "plx_set_tn2_stem": [_I],
