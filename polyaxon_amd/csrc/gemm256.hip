@@ -206,7 +206,9 @@ __device__ __forceinline__ float gelu_tanh_grad(float h) {
   const float k0 = 0.7978845608028654f, k1 = 0.044715f;
   const float e = __expf(2.f * k0 * fmaf(k1 * h * h, h, h));
   const float t = 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + e);
-  return fmaf(0.5f, 1.f + t, 0.5f * h * (1.f - t * t) * k0 * fmaf(3.f * k1, h * h, 1.f));
+  // h * h is capped below fp32's overflow: from |h| ~ 5 on, 1 - t t and the term with it are 0, but at |h| >= 2^64 the
+  // uncapped square is inf and 0 * inf made the derivative NaN instead of 0 or 1 (every smaller |h|: the same bits)
+  return fmaf(0.5f, 1.f + t, 0.5f * h * (1.f - t * t) * k0 * fmaf(3.f * k1, fminf(h * h, 3.0e38f), 1.f));
 }
 
 // Epilogue store layout.  An MFMA tile's lane holds 4 consecutive columns of one row, so storing tiles one by one
@@ -1192,6 +1194,14 @@ PLX_API int plx_gemm256_splits(int M, int N, int K) {
   if (M <= 0 || N <= 0 || K <= 0 || M % BM || N % BN || K % BK) return 0;
   const int kps = plan_kt_per_split(M, N, K);
   return (K / BK + kps - 1) / kps;
+}
+
+// diagnostics: K-tiles per split of that plan (plan_kt_per_split, the helper plx_gemm256_exv dispatches through): split
+// s runs K-tiles [s * kps, min(K / 64, (s + 1) * kps)), so the last one may be shorter (tests derive their chain
+// from it)
+PLX_API int plx_gemm256_kt_per_split(int M, int N, int K) {
+  if (M <= 0 || N <= 0 || K <= 0 || M % BM || N % BN || K % BK) return 0;
+  return plan_kt_per_split(M, N, K);
 }
 
 // A/B knob: blocks the split-K planner aims for (0 disables splitting)

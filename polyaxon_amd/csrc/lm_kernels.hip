@@ -383,7 +383,9 @@ __device__ __forceinline__ float gelu_tanh_grad(float h) {
   // this pass VALU-bound at ~3 TB/s
   const float e = __expf(2.f * k0 * fmaf(k1 * h * h, h, h));
   const float t = 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + e);
-  return fmaf(0.5f, 1.f + t, 0.5f * h * (1.f - t * t) * k0 * fmaf(3.f * k1, h * h, 1.f));
+  // h * h is capped below fp32's overflow: from |h| ~ 5 on, 1 - t t and the term with it are 0, but at |h| >= 2^64 the
+  // uncapped square is inf and 0 * inf made the derivative NaN instead of 0 or 1 (every smaller |h|: the same bits)
+  return fmaf(0.5f, 1.f + t, 0.5f * h * (1.f - t * t) * k0 * fmaf(3.f * k1, fminf(h * h, 3.0e38f), 1.f));
 }
 
 // GELU = true: x is dA (the gradient of gelu(h)) and the kernel also writes dh = dA * gelu'(h) (bf16, rounded
