@@ -20,6 +20,8 @@
 
 #include <stdint.h>
 
+#include <type_traits>
+
 namespace {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -814,6 +816,16 @@ __device__ __forceinline__ s16x4 ds_tr(uint32_t addr) {
     return r;
 }
 
+// ... with a compile-time byte offset in the instruction's 16-bit offset field: one address register serves a whole
+// sequence of reads
+template <int OFF>
+__device__ __forceinline__ s16x4 ds_tr_o(uint32_t addr) {
+    static_assert(OFF >= 0 && OFF < 65536, "16-bit offset field");
+    s16x4 r;
+    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF) : "memory");
+    return r;
+}
+
 // GATHER: 0 dense rows, 1 the pixel shifted by (dh, dw) (3x3 weight gradient), 2 the stem's packed super-pixel
 // window: chunk k / 8 of row (n, r, c) is super-pixel (2r - 3 + t / 4, c - 2 + t % 4), t = k / 8 (plx_stem_conv_fwd)
 template <int ROWB, int GATHER = 0, int BKR = BK>
@@ -1303,6 +1315,395 @@ __global__ void weight_prep_kernel(const float* __restrict__ w, __bf16* __restri
     }
 }
 
+// ------------------------------------------------------------- BN-dx data gradient + weight gradient, fused
+// The data gradient of gemm_nt_kernel<256, 64, ..., BNDX> (N = 64, K = 64 NK <= 256: ResNet layer 1's conv3 / downsample
+// convolutions) that also forms the convolution's weight gradient dW[K][64] += dy^T . x_in from the dy tiles it
+// produces, and therefore never stores dy: its only reader was the weight-gradient GEMM.
+//
+// Persistent: block b walks the 256-row tiles b, b + grid, ...; 8 waves, one block per CU.  Per K stage the block
+// produces the 256 x 64 dy tile into LDS exactly as gemm_nt_kernel does (same expression, same single rounding; wave w
+// owns rows 8 (8 i + w) + lane / 8), wave w computes rows [32 w, 32 w + 32) of dx with the MFMA operands and the K
+// order of gemm_nt_kernel (so dx is bit-identical), and the complete 64 (k) x 64 (n) weight-gradient sub-tile of the
+// stage over the tile's 256 rows: wave w owns k rows [16 (w / 2), +16) and n columns [32 (w % 2), +32), 8 row steps of
+// two MFMAs.  Its fp32 accumulators (NK x 2 MFMA tiles per wave) live across the tiles and are added into dW once, at
+// the end, with float atomics in whole 256-byte rows staged through LDS (wgrad_kernel ATOMIC).
+//
+// The weight-gradient MFMAs reduce over rows, so both operands come from ds_read_b64_tr_b16 (T10).  The produced dy
+// image keeps gemm_nt_kernel's row-major [256][128 B] form but is swizzled with tr_swz<128> instead of nt_swz: that
+// swizzle (chunk ^= 2 (row bit 1) + 4 (row bit 3)) is conflict-free for the transposed reads (rows q, q + 8 of one
+// parity land on distinct 32-byte bank spans) and for the row reads of the dx MFMAs (the 16-lane groups of
+// ds_read_b128 cover all 16 slots of the 256-byte bank row), so one image serves both.  The x_in tile [256][128 B] is
+// staged once per tile by LDS-DMA in the same swizzle.
+//
+// Epilogue: gemm_nt_kernel's arithmetic in two phases (all threads add D and store dx; threads 0-255 then form the
+// BatchNorm-backward sums in gemm_nt_kernel's thread mapping and row order, so the partial rows keep their rounding bit
+// for bit).  Before it, every wave issues the next tile's x_in / B DMAs and its stage-0 loads, so the loads are in
+// flight while the epilogue runs.  (Measurements and the resource table: profiles/dgrad_wgrad_fused.md.)
+template <int NK>
+__global__ void __launch_bounds__(512, 1)
+bndx_wgrad_kernel(const __bf16* __restrict__ G, const __bf16* __restrict__ B, __bf16* __restrict__ C, int M, int ldb,
+                  int ldc, const __bf16* __restrict__ D, int ldd, BnBwd bnr, const uint8_t* __restrict__ dmask, BnDx bd,
+                  const __bf16* __restrict__ Xin, float* __restrict__ dW, int lddw) {
+    constexpr int BM = 256, BN = 64, NW = 8, K = NK * BK;
+    constexpr int A_BYTES = BM * BK * 2, B_BYTES = BN * BK * 2, STAGE = A_BYTES + B_BYTES;
+    constexpr int XOFF = 2 * STAGE;                          // the x_in tile, behind the two stage buffers
+    constexpr int AI = BM / (8 * NW);                        // 16-byte chunks of a stage's A tile per thread
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+
+    const int ntm = (M + BM - 1) / BM;
+    if ((int)blockIdx.x >= ntm) return;                      // no tile: nothing to add
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int fr = lane & 15, fq = lane >> 4;
+
+    // staging: chunk i of this thread is row (8 i + wave) * 8 + lane / 8 of the tile, physical chunk lane % 8, logical
+    // chunk lc (the same for every i: rows step by 64, the swizzle reads row bits 1 and 3)
+    const int srow = wave * 8 + (lane >> 3);
+    const int lc8 = ((lane & 7) ^ tr_swz<128>(srow)) * 8;
+    const uint32_t b_off = (uint32_t)((srow * ldb + ((lane & 7) ^ nt_swz(srow)) * 8) * 2);
+    const __amdgpu_buffer_rsrc_t rg = buf_rsrc(G), rb = buf_rsrc(B), rx = buf_rsrc(bd.x), rc = buf_rsrc(bd.coef),
+                                 rxi = buf_rsrc(Xin);
+    uint32_t e_off[AI];
+    u32x4 gq[AI], xq[AI];
+    uint32_t mq[AI];
+    u32x4 cf[6];
+    auto set_tile = [&](int m0) {
+#pragma unroll
+        for (int i = 0; i < AI; ++i) {
+            const int gm = m0 + i * 64 + srow;
+            e_off[i] = gm < M ? (uint32_t)((gm * K + lc8) * 2) : OOB;
+        }
+    };
+    auto stage_x = [&](int m0) {                             // x_in rows are dense [M][64]
+#pragma unroll
+        for (int i = 0; i < AI; ++i) {
+            const int gm = m0 + i * 64 + srow;
+            blds16(rxi, gm < M ? (uint32_t)((gm * BN + lc8) * 2) : OOB, smem + XOFF + (i * NW + wave) * 1024);
+        }
+    };
+    auto stage_b = [&](int buf, int k0) { blds16(rb, b_off + (uint32_t)(k0 * 2), smem + buf * STAGE + A_BYTES + wave * 1024); };
+    auto load_a = [&](int k0) {
+#pragma unroll
+        for (int i = 0; i < AI; ++i) {
+            gq[i] = __builtin_amdgcn_raw_buffer_load_b128(rg, (int)e_off[i], k0 * 2, 0);
+            xq[i] = __builtin_amdgcn_raw_buffer_load_b128(rx, (int)e_off[i], k0 * 2, 0);
+        }
+        if (bd.mask != nullptr) {                            // 1 bit per element: byte (element offset / 8)
+            const __amdgpu_buffer_rsrc_t rm = buf_rsrc(bd.mask);
+#pragma unroll
+            for (int i = 0; i < AI; ++i)
+                mq[i] = __builtin_amdgcn_raw_buffer_load_b8(rm, (int)(e_off[i] == OOB ? OOB : e_off[i] >> 4), k0 >> 3, 0);
+        } else {
+#pragma unroll
+            for (int i = 0; i < AI; ++i) mq[i] = 0xffu;
+        }
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            cf[2 * r] = __builtin_amdgcn_raw_buffer_load_b128(rc, lc8 * 4, (r * K + k0) * 4, 0);
+            cf[2 * r + 1] = __builtin_amdgcn_raw_buffer_load_b128(rc, lc8 * 4 + 16, (r * K + k0) * 4, 0);
+        }
+    };
+    auto xform_a = [&](int buf) {                            // gemm_nt_kernel's xform_a: registers -> dy chunks -> image
+        char* base = smem + buf * STAGE;
+        const float* ca = (const float*)&cf[0];
+        const float* cb = (const float*)&cf[2];
+        const float* cd = (const float*)&cf[4];
+#pragma unroll
+        for (int i = 0; i < AI; ++i) {
+            const uint32_t* pg = (const uint32_t*)&gq[i];
+            const uint32_t* px = (const uint32_t*)&xq[i];
+            u32x4 o;
+            uint32_t* po = (uint32_t*)&o;
+            const uint32_t mb = mq[i];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float g0 = (mb >> (2 * j)) & 1u ? __uint_as_float(pg[j] << 16) : 0.f;
+                const float g1 = (mb >> (2 * j + 1)) & 1u ? __uint_as_float(pg[j] & 0xffff0000u) : 0.f;
+                const float x0 = __uint_as_float(px[j] << 16), x1 = __uint_as_float(px[j] & 0xffff0000u);
+                const float o0 = fmaf(ca[2 * j], g0, fmaf(cb[2 * j], x0, cd[2 * j]));
+                const float o1 = fmaf(ca[2 * j + 1], g1, fmaf(cb[2 * j + 1], x1, cd[2 * j + 1]));
+                po[j] = pack_bf16x2(o0, o1);
+            }
+            if (e_off[i] == OOB) o = u32x4{0u, 0u, 0u, 0u};
+            *(u32x4*)(base + (i * NW + wave) * 1024 + lane * 16) = o;
+        }
+    };
+
+    f32x4 accw[NK][2];                                       // dW: k rows kt * 64 + 16 (wave / 2) + ..., n 32 (wave % 2) + 16 j
+#pragma unroll
+    for (int a = 0; a < NK; ++a) accw[a][0] = accw[a][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int kt4 = wave >> 1, nt2 = (wave & 1) * 2;
+    // T10 addressing of this lane within a 32-row step: row 8 (lane / 16) + (lane % 16) / 4, columns c0 + 4 (lane % 4);
+    // byte offsets of its reads of the dy image (columns 16 (wave / 2) + ...) and the x_in image (32 (wave % 2) + 16 j +
+    // ...); the second half of a fragment is 4 rows down, +512 (the swizzle does not read row bit 2)
+    const int trow = 8 * fq + (fr >> 2), tcol = 4 * (fr & 3);
+    auto tr_off = [&](int col) {
+        return (uint32_t)(trow * 128 + (((col >> 3) ^ tr_swz<128>(trow)) << 4) + ((col >> 2) & 1) * 8);
+    };
+    const uint32_t wa_off = tr_off(kt4 * 16 + tcol), wx_off0 = tr_off(nt2 * 16 + tcol), wx_off1 = tr_off(nt2 * 16 + 16 + tcol);
+
+    // epilogue mapping (threads 0-255): gemm_nt_kernel<256, 64, ...>'s
+    constexpr int CROW = BN * 2 + 16, CHUNKS = BN / 8, RSTEP = 256 / CHUNKS, ITERS = BM / RSTEP;
+    char* const ep = smem + STAGE;                           // tile / reduction staging: the second stage buffer
+    const bool bnr_on = bnr.part != nullptr, d_on = D != nullptr;
+
+    int tm = blockIdx.x;
+    set_tile(tm * BM);
+    stage_x(tm * BM);
+    load_a(0);
+    stage_b(0, 0);
+    for (; tm < ntm; tm += gridDim.x) {
+        const int m0 = tm * BM;
+        f32x4 acc[4][2];
+#pragma unroll
+        for (int a = 0; a < 4; ++a) acc[a][0] = acc[a][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+        xform_a(0);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+#pragma unroll
+        for (int kt = 0; kt < NK; ++kt) {
+            const int cur = kt & 1;
+            if (kt + 1 < NK) {
+                load_a((kt + 1) * BK);
+                stage_b(cur ^ 1, (kt + 1) * BK);
+            }
+            const char* As = smem + cur * STAGE;
+            const char* Bs = As + A_BYTES;
+#pragma unroll
+            for (int kk = 0; kk < 2; ++kk) {                 // dx: two 32-deep MFMA steps per stage
+                bf16x8 fa[4], fb[2];
+#pragma unroll
+                for (int rn = 0; rn < 4; ++rn) {
+                    const int row = rn * 16 + fr;
+                    fa[rn] = *(const bf16x8*)(Bs + row * 128 + (((kk * 4 + fq) ^ nt_swz(row)) << 4));
+                }
+#pragma unroll
+                for (int rm = 0; rm < 2; ++rm) {
+                    const int row = wave * 32 + rm * 16 + fr;
+                    fb[rm] = *(const bf16x8*)(As + row * 128 + (((kk * 4 + fq) ^ tr_swz<128>(row)) << 4));
+                }
+#pragma unroll
+                for (int rn = 0; rn < 4; ++rn)
+#pragma unroll
+                    for (int rm = 0; rm < 2; ++rm)
+                        acc[rn][rm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[rn], fb[rm], acc[rn][rm], 0, 0, 0);
+            }
+            // dW: eight 32-row steps, two per wait, transposed fragments.  The reads are inline asm (wgrad_kernel): with
+            // the builtin, hipcc could not tell these images from the buffers the stage's DMAs are filling and put
+            // s_waitcnt vmcnt(0) in front of the first read -- the stage's loads drained before the MFMAs they should
+            // hide behind.  The asm wait carries the fragments, so no MFMA can be scheduled above it.
+            const uint32_t sa_ = lds_addr(As) + wa_off;
+            const uint32_t sx_[2] = {lds_addr(smem + XOFF) + wx_off0, lds_addr(smem + XOFF) + wx_off1};
+            auto dw_steps = [&](auto msc) {                  // steps ms, ms + 1
+                constexpr int O = decltype(msc)::value * 32 * 128;
+                s16x4 alo[2], ahi[2], xlo[2][2], xhi[2][2];
+                alo[0] = ds_tr_o<O>(sa_);
+                ahi[0] = ds_tr_o<O + 512>(sa_);
+                alo[1] = ds_tr_o<O + 4096>(sa_);
+                ahi[1] = ds_tr_o<O + 4608>(sa_);
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    xlo[0][j] = ds_tr_o<O>(sx_[j]);
+                    xhi[0][j] = ds_tr_o<O + 512>(sx_[j]);
+                    xlo[1][j] = ds_tr_o<O + 4096>(sx_[j]);
+                    xhi[1][j] = ds_tr_o<O + 4608>(sx_[j]);
+                }
+                asm volatile("s_waitcnt lgkmcnt(0)"
+                             : "+v"(alo[0]), "+v"(ahi[0]), "+v"(alo[1]), "+v"(ahi[1]), "+v"(xlo[0][0]), "+v"(xhi[0][0]),
+                               "+v"(xlo[0][1]), "+v"(xhi[0][1]), "+v"(xlo[1][0]), "+v"(xhi[1][0]), "+v"(xlo[1][1]),
+                               "+v"(xhi[1][1]));
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    const bf16x8 fw = __builtin_bit_cast(bf16x8, __builtin_shufflevector(alo[u], ahi[u], 0, 1, 2, 3, 4, 5, 6, 7));
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) {
+                        const bf16x8 fx =
+                            __builtin_bit_cast(bf16x8, __builtin_shufflevector(xlo[u][j], xhi[u][j], 0, 1, 2, 3, 4, 5, 6, 7));
+                        accw[kt][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw, fx, accw[kt][j], 0, 0, 0);
+                    }
+                }
+            };
+            dw_steps(std::integral_constant<int, 0>{});
+            dw_steps(std::integral_constant<int, 2>{});
+            dw_steps(std::integral_constant<int, 4>{});
+            dw_steps(std::integral_constant<int, 6>{});
+            __builtin_amdgcn_sched_barrier(0);               // the transform (it waits for the loads) stays behind the MFMAs
+            if (kt + 1 < NK) xform_a(cur ^ 1);               // the other buffer's readers retired at the last barrier
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+        }
+        // every LDS read of the tile is done: the next tile's x_in, B and stage-0 loads go out before the epilogue
+        const int tnext = tm + gridDim.x;
+        if (tnext < ntm) {
+            set_tile(tnext * BM);
+            stage_x(tnext * BM);
+            load_a(0);
+            stage_b(0, 0);
+        }
+        // gemm_nt_kernel's data-gradient epilogue (see there) in two phases, so that its operands fit the registers
+        // beside the next tile's loads and the dW accumulators.  The accumulators are parked in LDS first.  Phase A, all
+        // 512 threads (chunk column te % 8, rows te / 8 + 64 i): add D, store the dx rows, and put the final rows back
+        // into the staged tile.  Phase B, threads 0-255 in gemm_nt_kernel's mapping (rows te / 8 + 32 it, in order, so
+        // the partial sums keep their rounding): the BatchNorm-backward sums of the final rows.
+        const int rows = min(BM, M - m0);
+        // the thread's epilogue coordinates are formed per tile from an opaque copy of its id: hoisted out of the tile
+        // loop, the staging addresses of every row stayed live through the K loop and spilled
+        int te = tid;
+        asm volatile("" : "+v"(te));
+        const int cc = te % CHUNKS, ch0 = cc * 8;
+        const bool ep_thread = te < 256;
+#pragma unroll
+        for (int rm = 0; rm < 2; ++rm) {
+            const int ml = wave * 32 + rm * 16 + fr;
+#pragma unroll
+            for (int rn = 0; rn < 4; ++rn) {
+                const f32x4 v = acc[rn][rm];
+                uint2 packed;
+                packed.x = pack_bf16x2(v[0], v[1]);
+                packed.y = pack_bf16x2(v[2], v[3]);
+                *(uint2*)(ep + ml * CROW + (rn * 16 + fq * 4) * 2) = packed;
+            }
+        }
+        __syncthreads();
+        {
+            constexpr int AIT = BM / 64;
+            const int ra0 = te / CHUNKS;
+            int orow[AIT];
+            uint4 dpre[AIT];
+            uint32_t dmpre[AIT];
+#pragma unroll
+            for (int i = 0; i < AIT; ++i) orow[i] = min(m0 + ra0 + i * 64, M - 1);
+            if (d_on) {
+#pragma unroll
+                for (int i = 0; i < AIT; ++i) dpre[i] = *(const uint4*)(D + (size_t)orow[i] * ldd + ch0);
+                if (dmask != nullptr) {
+#pragma unroll
+                    for (int i = 0; i < AIT; ++i) dmpre[i] = dmask[((size_t)orow[i] * ldd + ch0) >> 3];
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < AIT; ++i) {
+                const int r = ra0 + i * 64;
+                if (r >= rows) break;
+                uint4 v = *(const uint4*)(ep + r * CROW + cc * 16);
+                if (d_on) {                                  // C = bf16(bf16(A.B^T) + D * mask)
+                    uint32_t* pv = (uint32_t*)&v;
+                    const uint32_t* pd = (const uint32_t*)&dpre[i];
+                    const uint32_t db = dmask != nullptr ? dmpre[i] : 0xffu;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const float d0 = (db >> (2 * j)) & 1u ? __uint_as_float(pd[j] << 16) : 0.f;
+                        const float d1 = (db >> (2 * j + 1)) & 1u ? __uint_as_float(pd[j] & 0xffff0000u) : 0.f;
+                        const float lo = __uint_as_float(pv[j] << 16) + d0;
+                        const float hi = __uint_as_float(pv[j] & 0xffff0000u) + d1;
+                        pv[j] = pack_bf16x2(lo, hi);
+                    }
+                    if (bnr_on) *(uint4*)(ep + r * CROW + cc * 16) = v;
+                }
+                *(uint4*)(C + (size_t)orow[i] * ldc + ch0) = v;
+            }
+        }
+        float sa[8], sb[8];
+        if (bnr_on) {
+            __syncthreads();                                 // the final rows are in the staged tile
+            if (ep_thread) {
+                const int r0 = te / CHUNKS;
+                float mu[8], is[8];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    sa[k] = sb[k] = 0.f;
+                    mu[k] = bnr.mean[ch0 + k];
+                    is[k] = bnr.invstd[ch0 + k];
+                }
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    constexpr int HI = ITERS / 2;
+                    asm volatile("" ::: "memory");            // the second pass's loads stay behind the first pass
+                    uint4 xpre[HI];
+                    uint32_t mpre[HI];
+#pragma unroll
+                    for (int i = 0; i < HI; ++i) {
+                        const size_t e = (size_t)min(m0 + r0 + (h * HI + i) * RSTEP, M - 1) * ldc + ch0;
+                        xpre[i] = *(const uint4*)(bnr.x + e);
+                        mpre[i] = bnr.mask != nullptr ? bnr.mask[e >> 3] : 0xffu;
+                    }
+                    if (bnr.skip_w > 0) {
+#pragma unroll
+                        for (int i = 0; i < HI; ++i) {
+                            const int gm = m0 + r0 + (h * HI + i) * RSTEP, q = gm / bnr.skip_w;
+                            if (((gm - q * bnr.skip_w) | (q % bnr.skip_h)) % 2 == 0) mpre[i] = 0u;
+                        }
+                    }
+#pragma unroll
+                    for (int i = 0; i < HI; ++i) {
+                        const int r = r0 + (h * HI + i) * RSTEP;
+                        if (r >= rows) break;
+                        const uint4 v = *(const uint4*)(ep + r * CROW + cc * 16);
+                        const uint32_t mb = mpre[i];
+                        const uint32_t* pv = (const uint32_t*)&v;
+                        const uint32_t* px = (const uint32_t*)&xpre[i];
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            const float g0 = (mb >> (2 * j)) & 1u ? __uint_as_float(pv[j] << 16) : 0.f;
+                            const float g1 = (mb >> (2 * j + 1)) & 1u ? __uint_as_float(pv[j] & 0xffff0000u) : 0.f;
+                            const float x0 = __uint_as_float(px[j] << 16), x1 = __uint_as_float(px[j] & 0xffff0000u);
+                            sa[2 * j] += g0;
+                            sa[2 * j + 1] += g1;
+                            sb[2 * j] = fmaf(g0, (x0 - mu[2 * j]) * is[2 * j], sb[2 * j]);
+                            sb[2 * j + 1] = fmaf(g1, (x1 - mu[2 * j + 1]) * is[2 * j + 1], sb[2 * j + 1]);
+                        }
+                    }
+                }
+            }
+        }
+        if (bnr_on) {                                        // gemm_nt_kernel's reduce_store: [256][17] floats over the tile
+            float* red = (float*)ep;
+            __syncthreads();
+            if (ep_thread) {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    red[te * 17 + k] = sa[k];
+                    red[te * 17 + 8 + k] = sb[k];
+                }
+            }
+            __syncthreads();
+            if (te < CHUNKS * 16) {
+                const int c = te % CHUNKS, v = te / CHUNKS;
+                float sum = 0.f;
+#pragma unroll 4
+                for (int j = 0; j < RSTEP; ++j) sum += red[(j * CHUNKS + c) * 17 + v];
+                float* pa = bnr.part + (size_t)(bnr.blk_off + tm) * ldc;
+                float* pb = bnr.part + (size_t)(bnr.part_ld + bnr.blk_off + tm) * ldc;
+                if (v < 8) pa[c * 8 + v] = sum;
+                else pb[c * 8 + v - 8] = sum;
+            }
+        }
+        // the next tile's first barrier (after its xform_a into buffer 0) retires the staging's readers before buffer 1
+        // is written again
+    }
+    // flush: the wave's dW tiles -> LDS [K][64 floats] (XOR-swizzled, conflict-free both ways), then whole 256-byte rows
+    // into dW with float atomics
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    float* red = (float*)smem;
+    static_assert(K * 256 <= 2 * STAGE, "the flush image fits the stage buffers");
+#pragma unroll
+    for (int kt = 0; kt < NK; ++kt)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = kt * 64 + kt4 * 16 + 4 * fq + r, col = (nt2 + j) * 16 + fr;
+                red[row * 64 + (col ^ (((row >> 2) & 3) << 4))] = accw[kt][j][r];
+            }
+    __syncthreads();
+#pragma unroll 4
+    for (int row = wave; row < K; row += NW) {
+        const float v = red[row * 64 + (lane ^ (((row >> 2) & 3) << 4))];
+        __hip_atomic_fetch_add(dW + (size_t)row * lddw + lane, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
 template <typename KernelT>
 int set_lds(KernelT k, int bytes) {
     return hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess ? 0
@@ -1360,6 +1761,31 @@ int launch_nt_prod(const void* A, const BnDx& bd, const BnApply& ba, const void*
     const int nwg = ((M + BM - 1) / BM) * (N / BN);
     hipLaunchKernelGGL(k, dim3(nwg), dim3(NTHREADS), LDS, s, (const __bf16*)A, (const __bf16*)B, (__bf16*)C, M, N, K, K,
                        ldb, ldc, stats, ConvGeom{}, (const __bf16*)D, ldd, bnr, dmask, bd, ba);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+// The fused BN-dx data gradient + weight gradient (bndx_wgrad_kernel): one persistent 8-wave block per CU, or `blocks`
+// of them (test hook: several tiles per block on small problems, blocks without a tile)
+template <int NK>
+int launch_bndx_wgrad(const void* g, const BnDx& bd, const void* Wt, void* C, int M, int ldb, int ldc, const void* D,
+                      int ldd, const BnBwd& bnr, const uint8_t* dmask, const void* x_in, float* dW, int lddw, int blocks,
+                      hipStream_t s) {
+    constexpr int LDS = 2 * (256 + 64) * BK * 2 + 256 * 64 * 2;
+    static_assert(LDS <= 160 * 1024, "LDS");
+    auto k = bndx_wgrad_kernel<NK>;
+    static int attr = set_lds(k, LDS);
+    if (attr) return attr;
+    int grid = blocks;
+    if (grid <= 0) {
+        int dev = 0, cus = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
+            return -3;
+        const int ntm = (M + 255) / 256;
+        grid = cus < ntm ? cus : ntm;
+    }
+    hipLaunchKernelGGL(k, dim3(grid), dim3(512), LDS, s, (const __bf16*)g, (const __bf16*)Wt, (__bf16*)C, M, ldb, ldc,
+                       (const __bf16*)D, ldd, bnr, dmask, bd, (const __bf16*)x_in, dW, lddw);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
@@ -1655,6 +2081,34 @@ int plx_gemm_nt_bndx(const void* g, const void* x, const uint8_t* mask, const fl
     return launch_nt_prod<256, 64, 4, 1, true, 0>(g, bd, {}, Wt, C, M, N, K, ldb, ldc, nullptr, s, D, ldd, b, dmask);
 }
 
+// plx_gemm_nt_bndx that also forms the convolution's weight gradient and therefore never writes dy (accepted, ignored):
+//   dW[K][N] (fp32, row stride lddw) += sum_m dy[m][k] * x_in[m][n]   with the bf16-rounded dy plx_gemm_nt_bndx stores
+// x_in: the convolution's saved input, dense bf16 [M][N].  C and the BatchNorm-backward partial rows are bit-identical to
+// plx_gemm_nt_bndx's.  N == 64 and K in {64, 128, 192, 256} only (the dW accumulators live in registers), else -1 and
+// nothing is launched.  dW is added into with float atomics (the summation order over row tiles is not fixed).
+// blocks: 0 = one persistent block per CU (at most one per 256-row tile); > 0 = that many blocks (test hook).
+int plx_gemm_nt_bndx_wgrad(const void* g, const void* x, const uint8_t* mask, const float* coef, void* dy,
+                           const void* Wt, void* C, int M, int N, int K, int ldb, int ldc, const void* D, int ldd,
+                           const uint8_t* dmask, const BnBwd* bnr, const void* x_in, float* dW, int lddw, int blocks,
+                           void* stream) {
+    (void)dy;
+    if (M <= 0 || N != 64 || K % BK || K < BK || K > 4 * BK || ldb % 8 || ldc % 8 || (D != nullptr && ldd % 8)) return -1;
+    if (g == nullptr || x == nullptr || coef == nullptr || x_in == nullptr || dW == nullptr || lddw < N || blocks < 0)
+        return -1;
+    if ((long)M * K >= (1l << 30)) return -1;             // 32-bit byte offsets into g / x
+    if (dmask != nullptr && (D == nullptr || ldd != N)) return -1;
+    if (bnr != nullptr && (ldc != N || bnr->part == nullptr)) return -1;
+    const BnBwd b = bnr != nullptr ? *bnr : BnBwd{};
+    const BnDx bd{(const __bf16*)x, mask, coef, nullptr};
+    hipStream_t s = (hipStream_t)stream;
+    switch (K / BK) {
+        case 1: return launch_bndx_wgrad<1>(g, bd, Wt, C, M, ldb, ldc, D, ldd, b, dmask, x_in, dW, lddw, blocks, s);
+        case 2: return launch_bndx_wgrad<2>(g, bd, Wt, C, M, ldb, ldc, D, ldd, b, dmask, x_in, dW, lddw, blocks, s);
+        case 3: return launch_bndx_wgrad<3>(g, bd, Wt, C, M, ldb, ldc, D, ldd, b, dmask, x_in, dW, lddw, blocks, s);
+        default: return launch_bndx_wgrad<4>(g, bd, Wt, C, M, ldb, ldc, D, ldd, b, dmask, x_in, dW, lddw, blocks, s);
+    }
+}
+
 // Forward of a 1x1 convolution whose input is the block output relu(bn(x) + residual) of the bottleneck before it,
 // produced in the kernel:
 //   out[M][K] = bf16(max(x * sb[k] + sb[K + k] + (res * ra[k] + rb[k]), 0)),  mask bit = (that sum > 0)
@@ -1692,6 +2146,9 @@ int plx_tn_plan_slices(int M, int N1, int N2, int num_cus, int v2) {
 void plx_set_tn2_c64(int on) { g_tn2_c64 = on ? 1 : 0; }
 
 void plx_set_tn_atomic(int on) { g_tn_atomic = on ? 1 : 0; }
+
+// the current setting (the Python side sends a weight gradient to the atomic-only fused kernel only when it is on)
+int plx_get_tn_atomic() { return g_tn_atomic; }
 
 void plx_set_tn2_stem(int mode) { g_tn2_stem = mode < 0 ? 0 : (mode > 2 ? 2 : mode); }
 

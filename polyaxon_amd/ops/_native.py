@@ -273,6 +273,7 @@ SIGNATURES: Dict[str, Dict[str, list]] = {
     "plx_conv": {
         "plx_gemm_nt": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P],
         "plx_gemm_nt_bndx": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P],
+        "plx_gemm_nt_bndx_wgrad": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _I, _I, _P],
         "plx_gemm_nt_bnapply": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P],
         "plx_gemm_nt_rows_per_block": [_I],
         "plx_gemm_nt_plan": [_I, _I, _I, _I],
@@ -281,6 +282,7 @@ SIGNATURES: Dict[str, Dict[str, list]] = {
         "plx_set_tn2_stem": [_I],
         "plx_set_tn2_c64": [_I],
         "plx_set_tn_atomic": [_I],
+        "plx_get_tn_atomic": [],
         "plx_tn_plan_slices": [_I, _I, _I, _I, _I],
         "plx_gemm_tn": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
         "plx_weight_prep": [_P, _P, _P, _I, _I, _P],

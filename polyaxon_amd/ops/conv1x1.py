@@ -55,6 +55,26 @@ def bn_apply_fused() -> bool:
     return _BN_APPLY_FUSED
 
 
+# A/B knob, read once at load: 1 = where a BatchNorm-dx data gradient (DxSink) belongs to a convolution with Cin = 64 and
+# Cout <= 256 whose weight gradient accumulates into its flat slot with atomics, one kernel forms both gradients and the
+# BatchNorm's dx is never stored (plx_gemm_nt_bndx_wgrad); 0 = plx_gemm_nt_bndx and the side stream's plx_gemm_tn
+_DGRAD_WGRAD_FUSED = os.environ.get("PLX_DGRAD_WGRAD_FUSED", "1") != "0"
+
+
+def set_dgrad_wgrad_fused(on: bool) -> bool:
+    """Switch the fused data + weight gradient for the backwards run from now on; returns the previous setting."""
+    global _DGRAD_WGRAD_FUSED
+    prev, _DGRAD_WGRAD_FUSED = _DGRAD_WGRAD_FUSED, bool(on)
+    return prev
+
+
+def dgrad_wgrad_fused_ok(cin: int, cout: int) -> bool:
+    """The shape class and mode of the fused data + weight gradient: one 64-wide N tile, at most four K stages (the dW
+    accumulators live in registers), and the atomic weight-gradient mode (the kernel has no deterministic reduction)."""
+    return (_DGRAD_WGRAD_FUSED and cin == 64 and cout <= 256 and cout % 64 == 0
+            and bool(_native.lib("plx_conv").plx_get_tn_atomic()))
+
+
 def _num_cus(dev: torch.device) -> int:
     idx = dev.index if dev.index is not None else torch.cuda.current_device()
     if idx not in _CUS:
@@ -142,6 +162,41 @@ def gemm_nt_bndx(g: torch.Tensor, x: torch.Tensor, mask: torch.Tensor, coef: tor
                                                   add_mask.data_ptr() if add_mask is not None else None,
                                                   ctypes.addressof(bnr) if bnr is not None else None, _stream())
     _native.check(rc, "plx_gemm_nt_bndx")
+    return out
+
+
+def gemm_nt_bndx_wgrad(g: torch.Tensor, x: torch.Tensor, mask: torch.Tensor, coef: torch.Tensor, dy: torch.Tensor,
+                       b: torch.Tensor, x_in: torch.Tensor, dw: torch.Tensor, out: torch.Tensor = None,
+                       add: torch.Tensor = None, bnr: "_native.GemmBnBwdArgs" = None, add_mask: torch.Tensor = None,
+                       blocks: int = 0) -> torch.Tensor:
+    """:func:`gemm_nt_bndx` that also adds the convolution's weight gradient ``dw[K][N] += dyᵀ · x_in`` (fp32, float
+    atomics) from the ``dy`` tiles it produces, and never stores ``dy`` (accepted, left untouched).  ``x_in``: the
+    convolution's saved input, dense bf16 ``[M][N]``; N = 64 and K ≤ 256 only.  ``out`` and the ``bnr`` partials are
+    bit-identical to :func:`gemm_nt_bndx`'s.  ``blocks``: 0 = one persistent block per CU; a test hook otherwise."""
+    m, k = g.shape
+    n = b.shape[0]
+    if out is None:
+        out = torch.empty(m, n, dtype=torch.bfloat16, device=g.device)
+    for t in (g, x, dy):
+        assert t.shape == (m, k) and t.dtype == torch.bfloat16 and t.stride() == (k, 1) and t.data_ptr() % 16 == 0
+    assert b.stride(1) == 1 and out.stride(1) == 1 and b.shape[1] == k and b.dtype == torch.bfloat16
+    assert b.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0
+    assert coef.dtype == torch.float32 and coef.is_contiguous() and coef.numel() == 3 * k
+    if mask is not None:
+        assert mask.dtype == torch.uint8 and mask.numel() == m * k // 8
+    assert x_in.shape == (m, n) and x_in.dtype == torch.bfloat16 and x_in.stride() == (n, 1) and x_in.data_ptr() % 16 == 0
+    assert dw.shape == (k, n) and dw.dtype == torch.float32 and dw.stride(1) == 1
+    _check_add(add, add_mask, m, n)
+    rc = _native.lib("plx_conv").plx_gemm_nt_bndx_wgrad(g.data_ptr(), x.data_ptr(),
+                                                        mask.data_ptr() if mask is not None else None,
+                                                        coef.data_ptr(), dy.data_ptr(), b.data_ptr(), out.data_ptr(),
+                                                        m, n, k, b.stride(0), out.stride(0),
+                                                        add.data_ptr() if add is not None else None,
+                                                        add.stride(0) if add is not None else 0,
+                                                        add_mask.data_ptr() if add_mask is not None else None,
+                                                        ctypes.addressof(bnr) if bnr is not None else None,
+                                                        x_in.data_ptr(), dw.data_ptr(), dw.stride(0), blocks, _stream())
+    _native.check(rc, "plx_gemm_nt_bndx_wgrad")
     return out
 
 
@@ -477,6 +532,7 @@ class _Conv1x1(torch.autograd.Function):
                                "backward could fill it")
         dy = dy.to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
         dx = dw = None
+        wgrad_done = False
         extra, extra_mask = ctx.box.take() if ctx.box is not None else (None, None)
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x, memory_format=torch.channels_last)
@@ -494,7 +550,17 @@ class _Conv1x1(torch.autograd.Function):
                 bnr = ctx.link.request(-(-(n * h * w) // rows))
             elif ctx.link is not None and ctx.sink is not None and ctx.sink.s2k1 and extra is None:
                 bnr = ctx.link.request_split(-(-(n * h * w) // rows), -(-(n * ((h + 1) // 2) * ((w + 1) // 2)) // rows))
-            if fused is not None:  # fills dy (the BatchNorm's dx) and reads it as the A operand
+            cout = ctx.wshape[0]
+            if (fused is not None and ctx.needs_input_grad[1] and ctx.wgrad is not None
+                    and dgrad_wgrad_fused_ok(cin, cout)):
+                # one kernel on this stream forms dx and adds dW into the flat slot from the BatchNorm's dx tiles, which
+                # are never stored: no weight-gradient launch follows
+                g, bx, bmask, coef, _ = fused
+                gemm_nt_bndx_wgrad(_rows(g), _rows(bx), bmask, coef, _rows(dy), wt, _rows(x),
+                                   ctx.wgrad.as_strided((cout, cin), (cin, 1)), _rows(dx),
+                                   add=_rows(extra) if extra is not None else None, bnr=bnr, add_mask=extra_mask)
+                wgrad_done = True
+            elif fused is not None:  # fills dy (the BatchNorm's dx) and reads it as the A operand
                 g, bx, bmask, coef, _ = fused
                 gemm_nt_bndx(_rows(g), _rows(bx), bmask, coef, _rows(dy), wt, _rows(dx),
                              add=_rows(extra) if extra is not None else None, bnr=bnr, add_mask=extra_mask)
@@ -504,7 +570,7 @@ class _Conv1x1(torch.autograd.Function):
             if ctx.sink is not None:  # the downsample conv's dgrad adds this gradient in its epilogue
                 ctx.sink.put(dx)
                 dx = None
-        if ctx.needs_input_grad[1]:
+        if ctx.needs_input_grad[1] and not wgrad_done:
             cout = ctx.wshape[0]
             if ctx.wgrad is not None:  # accumulate into the flat gradient slot, autograd sees no weight grad
                 slot = ctx.wgrad.as_strided((cout, cin), (cin, 1))
