@@ -44,15 +44,67 @@ __device__ __forceinline__ float block_sum(float v, float* sh) {
   return t;
 }
 
+// ------------------------------------------------------------------------------------------ residual dropout
+// The rate is device data (ops/dropout.py DropoutState): hp[0] threshold T = min(round(p * 65536), 65535), hp[1] the
+// bits of the fp32 scale c = 65536 / (65536 - T), hp[2..3] the Philox key; step[0] is the trainer's device step
+// counter, read at run time, so a replayed graph draws fresh bits every step and the backward of the same step
+// regenerates the forward's mask instead of loading one.  16-byte vector v (a 64-bit global index, independent of the
+// grid) of site `site` draws w = Philox4x32-10(counter = (v_lo, v_hi, step, site), key); element k takes the 16-bit
+// half (w[k >> 1] >> 16 * (k & 1)) & 0xffff and is kept iff half >= T.  T = 0 keeps everything with c = 1.0 exactly.
+struct DropArgs {
+  const uint32_t* hp;
+  const int32_t* step;
+  uint32_t site;
+};
+
+struct Drop {
+  uint32_t T, k0, k1, t, site;
+  float c;
+};
+
+__device__ __forceinline__ Drop drop_load(const DropArgs a) {
+  return Drop{a.hp[0], a.hp[2], a.hp[3], (uint32_t)a.step[0], a.site, __uint_as_float(a.hp[1])};
+}
+
+// bit k set: element k of vector v is kept
+__device__ __forceinline__ uint32_t drop_keep(const Drop& d, int64_t v) {
+  uint32_t c[4] = {(uint32_t)v, (uint32_t)((uint64_t)v >> 32), d.t, d.site};
+  uint32_t k0 = d.k0, k1 = d.k1;
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t lo0 = 0xD2511F53u * c[0], hi0 = __umulhi(0xD2511F53u, c[0]);
+    const uint32_t lo1 = 0xCD9E8D57u * c[2], hi1 = __umulhi(0xCD9E8D57u, c[2]);
+    c[0] = hi1 ^ c[1] ^ k0;
+    c[1] = lo1;
+    c[2] = hi0 ^ c[3] ^ k1;
+    c[3] = lo0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  uint32_t keep = 0;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) keep |= (uint32_t)(((c[k >> 1] >> (16 * (k & 1))) & 0xffffu) >= d.T) << k;
+  return keep;
+}
+
+// s = bf16(x + (keep ? c * res : 0)): fp32, one rounding
+__device__ __forceinline__ bf16x8 drop_add(const Drop& d, uint32_t keep, bf16x8 x, const bf16x8 res) {
+#pragma unroll
+  for (int k = 0; k < 8; ++k) x.v[k] = f2bf(fmaf(d.c, (keep >> k) & 1 ? bf2f(res.v[k]) : 0.f, bf2f(x.v[k])));
+  return x;
+}
+
 // ADD: the residual add feeding the norm is fused in -- s = bf16(x + res) is written (the next residual) and
-// normalised; the second pass re-reads the s chunk this same thread wrote.
-template <bool ADD = false>
-__global__ __launch_bounds__(kBlock) void rms_fwd_kernel(const bf16x8* __restrict__ x, const float* __restrict__ w,
-                                                         bf16x8* __restrict__ y, float* __restrict__ rstd_out,
-                                                         int64_t rows, int dv, float eps,
-                                                         const bf16x8* __restrict__ res = nullptr,
-                                                         bf16x8* __restrict__ s_out = nullptr) {
+// normalised; the second pass re-reads the s chunk this same thread wrote.  DROP: res goes through the dropout mask
+// first.  The kernels below instantiate these bodies.
+template <bool ADD, bool DROP>
+__device__ __forceinline__ void rms_fwd_body(const bf16x8* __restrict__ x, const float* __restrict__ w,
+                                             bf16x8* __restrict__ y, float* __restrict__ rstd_out, int64_t rows, int dv,
+                                             float eps, const bf16x8* __restrict__ res, bf16x8* __restrict__ s_out,
+                                             const DropArgs da) {
   __shared__ float sh[kBlock / 64];
+  Drop dr = {};
+  if (DROP) dr = drop_load(da);
   for (int64_t r = blockIdx.x; r < rows; r += gridDim.x) {
     const bf16x8* xr = ADD ? s_out + r * dv : x + r * dv;  // pass 2 reads the sum
     float ss = 0.f;
@@ -60,8 +112,12 @@ __global__ __launch_bounds__(kBlock) void rms_fwd_kernel(const bf16x8* __restric
       bf16x8 v = x[r * dv + i];
       if (ADD) {
         const bf16x8 rv = res[r * dv + i];
+        if (DROP) {
+          v = drop_add(dr, drop_keep(dr, r * dv + i), v, rv);
+        } else {
 #pragma unroll
-        for (int k = 0; k < 8; ++k) v.v[k] = f2bf(bf2f(v.v[k]) + bf2f(rv.v[k]));
+          for (int k = 0; k < 8; ++k) v.v[k] = f2bf(bf2f(v.v[k]) + bf2f(rv.v[k]));
+        }
         s_out[r * dv + i] = v;
       }
 #pragma unroll
@@ -83,14 +139,34 @@ __global__ __launch_bounds__(kBlock) void rms_fwd_kernel(const bf16x8* __restric
   }
 }
 
-// ADD: dx = RMSNorm backward + dres (the residual path's gradient), fp32 sum rounded once
 template <bool ADD = false>
-__global__ __launch_bounds__(kBlock) void rms_bwd_kernel(const bf16x8* __restrict__ x, const float* __restrict__ w,
-                                                         const bf16x8* __restrict__ dy, const float* __restrict__ rstd_in,
-                                                         bf16x8* __restrict__ dx, float* __restrict__ dw_part,
-                                                         int64_t rows, int dv,
-                                                         const bf16x8* __restrict__ dres = nullptr) {
+__global__ __launch_bounds__(kBlock) void rms_fwd_kernel(const bf16x8* __restrict__ x, const float* __restrict__ w,
+                                                         bf16x8* __restrict__ y, float* __restrict__ rstd_out,
+                                                         int64_t rows, int dv, float eps,
+                                                         const bf16x8* __restrict__ res = nullptr,
+                                                         bf16x8* __restrict__ s_out = nullptr) {
+  rms_fwd_body<ADD, false>(x, w, y, rstd_out, rows, dv, eps, res, s_out, DropArgs{});
+}
+
+__global__ __launch_bounds__(kBlock) void rms_fwd_drop_kernel(const bf16x8* __restrict__ x, const float* __restrict__ w,
+                                                              bf16x8* __restrict__ y, float* __restrict__ rstd_out,
+                                                              int64_t rows, int dv, float eps,
+                                                              const bf16x8* __restrict__ res,
+                                                              bf16x8* __restrict__ s_out, const DropArgs da) {
+  rms_fwd_body<true, true>(x, w, y, rstd_out, rows, dv, eps, res, s_out, da);
+}
+
+// ADD: dx = RMSNorm backward + dres (the residual path's gradient), fp32 sum rounded once.  DROP: the same fp32 value
+// g also leaves as dres_out = bf16(keep ? c * g : +0), the gradient of the dropped-out branch.
+template <bool ADD, bool DROP>
+__device__ __forceinline__ void rms_bwd_body(const bf16x8* __restrict__ x, const float* __restrict__ w,
+                                             const bf16x8* __restrict__ dy, const float* __restrict__ rstd_in,
+                                             bf16x8* __restrict__ dx, float* __restrict__ dw_part, int64_t rows, int dv,
+                                             const bf16x8* __restrict__ dres, bf16x8* __restrict__ dres_out,
+                                             const DropArgs da) {
   __shared__ float sh[kBlock / 64];
+  Drop drp = {};
+  if (DROP) drp = drop_load(da);
   float dwacc[kMaxVecPerLane][8];
 #pragma unroll
   for (int j = 0; j < kMaxVecPerLane; ++j)
@@ -120,14 +196,18 @@ __global__ __launch_bounds__(kBlock) void rms_bwd_kernel(const bf16x8* __restric
         const bf16x8 xv = x[r * dv + i], gv = dy[r * dv + i];
         bf16x8 dr = {};
         if (ADD) dr = dres[r * dv + i];
-        bf16x8 o;
+        const uint32_t keep = DROP ? drop_keep(drp, r * dv + i) : 0u;
+        bf16x8 o, od;
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
           const float xh = bf2f(xv.v[k]) * rstd;
           const float g = rstd * (bf2f(gv.v[k]) * w[i * 8 + k] - xh * mean_dot);
-          o.v[k] = f2bf(ADD ? g + bf2f(dr.v[k]) : g);
+          const float gt = ADD ? g + bf2f(dr.v[k]) : g;
+          o.v[k] = f2bf(gt);
+          if (DROP) od.v[k] = f2bf((keep >> k) & 1 ? drp.c * gt : 0.f);
         }
         dx[r * dv + i] = o;
+        if (DROP) dres_out[r * dv + i] = od;
       }
     }
   }
@@ -141,6 +221,24 @@ __global__ __launch_bounds__(kBlock) void rms_bwd_kernel(const bf16x8* __restric
   }
 }
 
+template <bool ADD = false>
+__global__ __launch_bounds__(kBlock) void rms_bwd_kernel(const bf16x8* __restrict__ x, const float* __restrict__ w,
+                                                         const bf16x8* __restrict__ dy, const float* __restrict__ rstd_in,
+                                                         bf16x8* __restrict__ dx, float* __restrict__ dw_part,
+                                                         int64_t rows, int dv,
+                                                         const bf16x8* __restrict__ dres = nullptr) {
+  rms_bwd_body<ADD, false>(x, w, dy, rstd_in, dx, dw_part, rows, dv, dres, nullptr, DropArgs{});
+}
+
+template <bool ADD>
+__global__ __launch_bounds__(kBlock) void rms_bwd_drop_kernel(const bf16x8* __restrict__ x, const float* __restrict__ w,
+                                                              const bf16x8* __restrict__ dy,
+                                                              const float* __restrict__ rstd_in, bf16x8* __restrict__ dx,
+                                                              float* __restrict__ dw_part, int64_t rows, int dv,
+                                                              const bf16x8* __restrict__ dres,
+                                                              bf16x8* __restrict__ dres_out, const DropArgs da) {
+  rms_bwd_body<ADD, true>(x, w, dy, rstd_in, dx, dw_part, rows, dv, dres, dres_out, da);
+}
 
 // ------------------------------------------------------------------------------------------------ LayerNorm
 __global__ __launch_bounds__(kBlock) void ln_fwd_kernel(const bf16x8* __restrict__ x, const float* __restrict__ w,
@@ -267,13 +365,15 @@ __device__ __forceinline__ float wave_sum(float v) {
 
 // ADD: the residual add feeding the norm is fused in: s = bf16(x + res) is written (the next residual) and
 // normalised -- one pass instead of an add kernel (3 row streams) followed by the norm (2).
-template <int VPL, bool ADD = false>
-__global__ __launch_bounds__(kBlock) void ln_fwd_wave_kernel(const bf16x8* __restrict__ x, const float* __restrict__ w,
-                                                             const float* __restrict__ bias, bf16x8* __restrict__ y,
-                                                             float* __restrict__ mean_out, float* __restrict__ rstd_out,
-                                                             int64_t rows, int dv, float eps,
-                                                             const bf16x8* __restrict__ res = nullptr,
-                                                             bf16x8* __restrict__ s_out = nullptr) {
+// DROP: res goes through the dropout mask first (drop_add)
+template <int VPL, bool ADD, bool DROP>
+__device__ __forceinline__ void ln_fwd_wave_body(const bf16x8* __restrict__ x, const float* __restrict__ w,
+                                                 const float* __restrict__ bias, bf16x8* __restrict__ y,
+                                                 float* __restrict__ mean_out, float* __restrict__ rstd_out,
+                                                 int64_t rows, int dv, float eps, const bf16x8* __restrict__ res,
+                                                 bf16x8* __restrict__ s_out, const DropArgs da) {
+  Drop dr = {};
+  if (DROP) dr = drop_load(da);
   const int lane = threadIdx.x & 63;
   const float inv_d = 1.f / (float)(dv * 8);
   const int64_t nw = (int64_t)gridDim.x * (kBlock / 64);
@@ -287,8 +387,12 @@ __global__ __launch_bounds__(kBlock) void ln_fwd_wave_kernel(const bf16x8* __res
       bf16x8 v = i < dv ? xr[i] : bf16x8{};
       if (ADD && i < dv) {
         const bf16x8 rv = res[r * dv + i];
+        if (DROP) {
+          v = drop_add(dr, drop_keep(dr, r * dv + i), v, rv);
+        } else {
 #pragma unroll
-        for (int k = 0; k < 8; ++k) v.v[k] = f2bf(bf2f(v.v[k]) + bf2f(rv.v[k]));
+          for (int k = 0; k < 8; ++k) v.v[k] = f2bf(bf2f(v.v[k]) + bf2f(rv.v[k]));
+        }
         s_out[r * dv + i] = v;
       }
 #pragma unroll
@@ -327,16 +431,39 @@ __global__ __launch_bounds__(kBlock) void ln_fwd_wave_kernel(const bf16x8* __res
   }
 }
 
-// ADD: dx = LN backward + dres (the gradient arriving through the residual path), summed in fp32 and rounded once:
-// the backward of the fused add + norm (both of its inputs get this same gradient)
 template <int VPL, bool ADD = false>
-__global__ __launch_bounds__(kBlock) void ln_bwd_wave_kernel(const bf16x8* __restrict__ x, const float* __restrict__ w,
-                                                             const bf16x8* __restrict__ dy,
-                                                             const float* __restrict__ mean_in,
-                                                             const float* __restrict__ rstd_in, bf16x8* __restrict__ dx,
-                                                             float* __restrict__ dw_part, float* __restrict__ db_part,
-                                                             int64_t rows, int dv,
-                                                             const bf16x8* __restrict__ dres = nullptr) {
+__global__ __launch_bounds__(kBlock) void ln_fwd_wave_kernel(const bf16x8* __restrict__ x, const float* __restrict__ w,
+                                                             const float* __restrict__ bias, bf16x8* __restrict__ y,
+                                                             float* __restrict__ mean_out, float* __restrict__ rstd_out,
+                                                             int64_t rows, int dv, float eps,
+                                                             const bf16x8* __restrict__ res = nullptr,
+                                                             bf16x8* __restrict__ s_out = nullptr) {
+  ln_fwd_wave_body<VPL, ADD, false>(x, w, bias, y, mean_out, rstd_out, rows, dv, eps, res, s_out, DropArgs{});
+}
+
+template <int VPL>
+__global__ __launch_bounds__(kBlock) void ln_fwd_wave_drop_kernel(const bf16x8* __restrict__ x,
+                                                                  const float* __restrict__ w,
+                                                                  const float* __restrict__ bias, bf16x8* __restrict__ y,
+                                                                  float* __restrict__ mean_out,
+                                                                  float* __restrict__ rstd_out, int64_t rows, int dv,
+                                                                  float eps, const bf16x8* __restrict__ res,
+                                                                  bf16x8* __restrict__ s_out, const DropArgs da) {
+  ln_fwd_wave_body<VPL, true, true>(x, w, bias, y, mean_out, rstd_out, rows, dv, eps, res, s_out, da);
+}
+
+// ADD: dx = LN backward + dres (the gradient arriving through the residual path), summed in fp32 and rounded once:
+// the backward of the fused add + norm (both of its inputs get this same gradient).  DROP: x gets that dx and the
+// dropped-out branch gets dres_out = bf16(keep ? c * g : +0) from the same fp32 value g that dx is rounded from.
+template <int VPL, bool ADD, bool DROP>
+__device__ __forceinline__ void ln_bwd_wave_body(const bf16x8* __restrict__ x, const float* __restrict__ w,
+                                                 const bf16x8* __restrict__ dy, const float* __restrict__ mean_in,
+                                                 const float* __restrict__ rstd_in, bf16x8* __restrict__ dx,
+                                                 float* __restrict__ dw_part, float* __restrict__ db_part, int64_t rows,
+                                                 int dv, const bf16x8* __restrict__ dres, bf16x8* __restrict__ dres_out,
+                                                 const DropArgs da) {
+  Drop drp = {};
+  if (DROP) drp = drop_load(da);
   __shared__ float shw[kBlock / 64][VPL * 64 * 8];
   __shared__ float shb[kBlock / 64][VPL * 64 * 8];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -374,16 +501,25 @@ __global__ __launch_bounds__(kBlock) void ln_bwd_wave_kernel(const bf16x8* __res
     for (int j = 0; j < VPL; ++j) {
       const int i = lane + j * 64;
       if (i < dv) {
-        bf16x8 o;
+        bf16x8 o, od;
+        float g[8];
         if (ADD) {
           const bf16x8 dr = dres[r * dv + i];
 #pragma unroll
-          for (int k = 0; k < 8; ++k) o.v[k] = f2bf(fmaf(rstd, gw[j][k] - mg - xh[j][k] * mgx, bf2f(dr.v[k])));
+          for (int k = 0; k < 8; ++k) g[k] = fmaf(rstd, gw[j][k] - mg - xh[j][k] * mgx, bf2f(dr.v[k]));
         } else {
 #pragma unroll
-          for (int k = 0; k < 8; ++k) o.v[k] = f2bf(rstd * (gw[j][k] - mg - xh[j][k] * mgx));
+          for (int k = 0; k < 8; ++k) g[k] = rstd * (gw[j][k] - mg - xh[j][k] * mgx);
         }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) o.v[k] = f2bf(g[k]);
         dx[r * dv + i] = o;
+        if (DROP) {
+          const uint32_t keep = drop_keep(drp, r * dv + i);
+#pragma unroll
+          for (int k = 0; k < 8; ++k) od.v[k] = f2bf((keep >> k) & 1 ? drp.c * g[k] : 0.f);
+          dres_out[r * dv + i] = od;
+        }
       }
     }
   }
@@ -404,6 +540,42 @@ __global__ __launch_bounds__(kBlock) void ln_bwd_wave_kernel(const bf16x8* __res
     dw_part[(int64_t)blockIdx.x * d + c] = ((shw[0][c] + shw[1][c]) + shw[2][c]) + shw[3][c];
     db_part[(int64_t)blockIdx.x * d + c] = ((shb[0][c] + shb[1][c]) + shb[2][c]) + shb[3][c];
   }
+}
+
+template <int VPL, bool ADD = false>
+__global__ __launch_bounds__(kBlock) void ln_bwd_wave_kernel(const bf16x8* __restrict__ x, const float* __restrict__ w,
+                                                             const bf16x8* __restrict__ dy,
+                                                             const float* __restrict__ mean_in,
+                                                             const float* __restrict__ rstd_in, bf16x8* __restrict__ dx,
+                                                             float* __restrict__ dw_part, float* __restrict__ db_part,
+                                                             int64_t rows, int dv,
+                                                             const bf16x8* __restrict__ dres = nullptr) {
+  ln_bwd_wave_body<VPL, ADD, false>(x, w, dy, mean_in, rstd_in, dx, dw_part, db_part, rows, dv, dres, nullptr,
+                                    DropArgs{});
+}
+
+template <int VPL, bool ADD>
+__global__ __launch_bounds__(kBlock) void ln_bwd_wave_drop_kernel(
+    const bf16x8* __restrict__ x, const float* __restrict__ w, const bf16x8* __restrict__ dy,
+    const float* __restrict__ mean_in, const float* __restrict__ rstd_in, bf16x8* __restrict__ dx,
+    float* __restrict__ dw_part, float* __restrict__ db_part, int64_t rows, int dv, const bf16x8* __restrict__ dres,
+    bf16x8* __restrict__ dres_out, const DropArgs da) {
+  ln_bwd_wave_body<VPL, ADD, true>(x, w, dy, mean_in, rstd_in, dx, dw_part, db_part, rows, dv, dres, dres_out, da);
+}
+
+// y = keep ? c * x : 0 over n_vec 16-byte vectors, one per thread: the dropout sites with no norm to fuse into (the
+// embedding sum, the checkpointed block, add + LayerNorm above d = 1024) and, on the gradient, their backward
+__global__ __launch_bounds__(kBlock) void dropout_kernel(const bf16x8* __restrict__ x, bf16x8* __restrict__ y,
+                                                         int64_t n_vec, const DropArgs da) {
+  const int64_t v = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (v >= n_vec) return;
+  const Drop d = drop_load(da);
+  const uint32_t keep = drop_keep(d, v);
+  const bf16x8 xv = x[v];
+  bf16x8 o;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) o.v[k] = f2bf((keep >> k) & 1 ? d.c * bf2f(xv.v[k]) : 0.f);
+  y[v] = o;
 }
 
 // ----------------------------------------------------------------------------- partial rows -> parameter gradient
@@ -609,5 +781,72 @@ PLX_API int plx_add_rms_backward(const void* s, const float* w, const void* dy, 
   if (d % 8 || d > kBlock * 8 * kMaxVecPerLane || rows <= 0) return 1;
   hipLaunchKernelGGL(rms_bwd_kernel<true>, dim3(plx_rms_bwd_blocks(rows)), dim3(kBlock), 0, stream, (const bf16x8*)s, w,
                      (const bf16x8*)dy, rstd, (bf16x8*)dx, dw_part, rows, d / 8, (const bf16x8*)dres);
+  return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------ residual dropout
+// The fused pairs with the dropout mask on res (contract above DropArgs).  hp: the 4 words of ops/dropout.py
+// DropoutState, step: the device step counter, site: the dropout site.  1 (nothing launched) on the shapes the plain
+// twins do not take and on a null hp / step.
+PLX_API int plx_add_ln_drop_forward(const void* x, const void* res, const float* w, const float* b, void* s, void* y,
+                                    float* mean, float* rstd, int64_t rows, int d, float eps, const void* hp,
+                                    const void* step, int site, hipStream_t stream) {
+  const int vpl = d > 0 ? ln_vpl(d) : 0;
+  if (d % 8 || !vpl || rows <= 0 || !hp || !step) return 1;
+  int64_t g = (rows + 3) / 4;
+  if (g > 8192) g = 8192;
+  const DropArgs da{(const uint32_t*)hp, (const int32_t*)step, (uint32_t)site};
+  hipLaunchKernelGGL(vpl == 1 ? ln_fwd_wave_drop_kernel<1> : ln_fwd_wave_drop_kernel<2>, dim3((int)g), dim3(kBlock), 0,
+                     stream, (const bf16x8*)x, w, b, (bf16x8*)y, mean, rstd, rows, d / 8, eps, (const bf16x8*)res,
+                     (bf16x8*)s, da);
+  return (int)hipGetLastError();
+}
+
+// dx = LN backward(s, dy) + ds (ds may be null: no gradient arrived on s), dres = its dropped-out copy
+PLX_API int plx_add_ln_drop_backward(const void* s, const float* w, const void* dy, const float* mean,
+                                     const float* rstd, const void* ds, void* dx, void* dres, float* dw_part,
+                                     float* db_part, int64_t rows, int d, const void* hp, const void* step, int site,
+                                     hipStream_t stream) {
+  const int vpl = d > 0 ? ln_vpl(d) : 0;
+  if (d % 8 || !vpl || rows <= 0 || !hp || !step) return 1;
+  const DropArgs da{(const uint32_t*)hp, (const int32_t*)step, (uint32_t)site};
+  auto k = vpl == 1 ? (ds ? ln_bwd_wave_drop_kernel<1, true> : ln_bwd_wave_drop_kernel<1, false>)
+                    : (ds ? ln_bwd_wave_drop_kernel<2, true> : ln_bwd_wave_drop_kernel<2, false>);
+  hipLaunchKernelGGL(k, dim3(plx_ln_bwd_blocks(rows, d)), dim3(kBlock), 0, stream, (const bf16x8*)s, w,
+                     (const bf16x8*)dy, mean, rstd, (bf16x8*)dx, dw_part, db_part, rows, d / 8, (const bf16x8*)ds,
+                     (bf16x8*)dres, da);
+  return (int)hipGetLastError();
+}
+
+PLX_API int plx_add_rms_drop_forward(const void* x, const void* res, const float* w, void* s, void* y, float* rstd,
+                                     int64_t rows, int d, float eps, const void* hp, const void* step, int site,
+                                     hipStream_t stream) {
+  if (d <= 0 || d % 8 || d > kBlock * 8 * kMaxVecPerLane || rows <= 0 || !hp || !step) return 1;
+  int64_t g = rows < 4096 ? rows : 4096;
+  const DropArgs da{(const uint32_t*)hp, (const int32_t*)step, (uint32_t)site};
+  hipLaunchKernelGGL(rms_fwd_drop_kernel, dim3((int)g), dim3(kBlock), 0, stream, (const bf16x8*)x, w, (bf16x8*)y, rstd,
+                     rows, d / 8, eps, (const bf16x8*)res, (bf16x8*)s, da);
+  return (int)hipGetLastError();
+}
+
+PLX_API int plx_add_rms_drop_backward(const void* s, const float* w, const void* dy, const float* rstd, const void* ds,
+                                      void* dx, void* dres, float* dw_part, int64_t rows, int d, const void* hp,
+                                      const void* step, int site, hipStream_t stream) {
+  if (d <= 0 || d % 8 || d > kBlock * 8 * kMaxVecPerLane || rows <= 0 || !hp || !step) return 1;
+  const DropArgs da{(const uint32_t*)hp, (const int32_t*)step, (uint32_t)site};
+  hipLaunchKernelGGL(ds ? rms_bwd_drop_kernel<true> : rms_bwd_drop_kernel<false>, dim3(plx_rms_bwd_blocks(rows)),
+                     dim3(kBlock), 0, stream, (const bf16x8*)s, w, (const bf16x8*)dy, rstd, (bf16x8*)dx, dw_part, rows,
+                     d / 8, (const bf16x8*)ds, (bf16x8*)dres, da);
+  return (int)hipGetLastError();
+}
+
+// y = keep ? c * x : 0 over n_vec 16-byte vectors (8 bf16 each); forward and backward of a standalone site
+PLX_API int plx_dropout(const void* x, void* y, int64_t n_vec, const void* hp, const void* step, int site,
+                        hipStream_t stream) {
+  const int64_t blocks = (n_vec + kBlock - 1) / kBlock;
+  if (n_vec <= 0 || blocks > 0x7fffffff || !hp || !step) return 1;
+  const DropArgs da{(const uint32_t*)hp, (const int32_t*)step, (uint32_t)site};
+  hipLaunchKernelGGL(dropout_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, stream, (const bf16x8*)x, (bf16x8*)y,
+                     n_vec, da);
   return (int)hipGetLastError();
 }

@@ -167,8 +167,14 @@ class Block(nn.Module):
             lambda d: _rms.LayerNorm(d, eps=cfg.norm_eps))  # fused bf16 LayerNorm (csrc/rmsnorm.hip)
         self.n1, self.n2 = Norm(cfg.d_model), Norm(cfg.d_model)
         self.attn, self.mlp = Attention(cfg), MLP(cfg)
+        self._drop = None  # (DropoutState, layer index): Transformer.set_dropout
 
     def forward(self, x, rope=None):
+        if self._drop is not None and self.training:
+            # the activation-checkpoint path: the recomputation runs at the same step, so it draws the same masks
+            state, l = self._drop
+            x = x + _rms.dropout(self.attn(self.n1(x), rope), state, 2 * l)
+            return x + _rms.dropout(self.mlp(self.n2(x)), state, 2 * l + 1)
         x = x + self.attn(self.n1(x), rope)
         return x + self.mlp(self.n2(x))
 
@@ -190,7 +196,16 @@ class Transformer(nn.Module):
         else:
             self.logit_mask = None
         self._rope = None
+        self._drop = None
         self.reset_parameters()
+
+    def set_dropout(self, state) -> None:
+        """Residual dropout (GPT-2's ``resid_pdrop`` / ``embd_pdrop``) with its rate in device memory (ops/dropout.py
+        DropoutState): site 2 l after the attention of block l, 2 l + 1 after its MLP, 2 n_layers on the embedding
+        sum.  None, or ``eval()``: every site is the plain code path."""
+        self._drop = state
+        for l, blk in enumerate(self.blocks):
+            blk._drop = None if state is None else (state, l)
 
     def init_spec(self):
         """(param, kind, scale) for the fused in-place re-initialiser (GPT-2 / Llama conventions)."""
@@ -225,16 +240,20 @@ class Transformer(nn.Module):
             if self._rope is None or self._rope[0].shape[0] < S or self._rope[0].device != tokens.device:
                 self._rope = rope_cache(max(S, 16), self.cfg.head_dim, self.cfg.rope_theta, tokens.device)
             rope = (self._rope[0][:S], self._rope[1][:S])  # fp32 tables; the attention casts as needed
+        drop = self._drop if self.training else None
+        if drop is not None:
+            x = _rms.dropout(x, drop, 2 * self.cfg.n_layers)
         if not (self.cfg.checkpoint and self.training):
             # every residual add is fused into the norm that reads its sum (ops/rmsnorm.py add_layer_norm /
-            # add_rms_norm) -- the same computation as Block.forward, one pass fewer over the residual per add
-            r = None
+            # add_rms_norm) -- the same computation as Block.forward, one pass fewer over the residual per add; with
+            # dropout the branch r of site `site` is masked inside that same pass
+            r, site = None, -1
             for blk in self.blocks:
-                x, h = self._add_norm(x, r, blk.n1)
-                r = blk.attn(h, rope)
-                x, h = self._add_norm(x, r, blk.n2)
-                r = blk.mlp(h)
-            x = self._add_norm(x, r, self.norm)[1]
+                x, h = self._add_norm(x, r, blk.n1, drop, site)
+                r, site = blk.attn(h, rope), site + 1
+                x, h = self._add_norm(x, r, blk.n2, drop, site)
+                r, site = blk.mlp(h), site + 1
+            x = self._add_norm(x, r, self.norm, drop, site)[1]
         else:
             for blk in self.blocks:
                 if self.cfg.checkpoint and self.training:
@@ -250,9 +269,13 @@ class Transformer(nn.Module):
         return lm_ops.linear(x, w, self.logit_mask, side=True)
 
     @staticmethod
-    def _add_norm(x, r, norm):
+    def _add_norm(x, r, norm, drop=None, site=0):
         if r is None:
             return x, norm(x)
+        if drop is not None:
+            if isinstance(norm, RMSNorm):
+                return _rms.add_rms_norm(x, r, norm.weight, norm.eps, drop=(drop, site))
+            return _rms.add_layer_norm(x, r, norm.weight, norm.bias, norm.eps, drop=(drop, site))
         if isinstance(norm, RMSNorm):
             return _rms.add_rms_norm(x, r, norm.weight, norm.eps)
         return _rms.add_layer_norm(x, r, norm.weight, norm.bias, norm.eps)

@@ -355,6 +355,11 @@ SIGNATURES: Dict[str, Dict[str, list]] = {
         "plx_add_rms_forward": [_P, _P, _P, _P, _P, _P, _L, _I, _F, _P],
         "plx_add_rms_backward": [_P, _P, _P, _P, _P, _P, _P, _L, _I, _P],
         "plx_add_ln_backward": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _P],
+        "plx_add_ln_drop_forward": [_P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _F, _P, _P, _I, _P],
+        "plx_add_ln_drop_backward": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _P, _P, _I, _P],
+        "plx_add_rms_drop_forward": [_P, _P, _P, _P, _P, _P, _L, _I, _F, _P, _P, _I, _P],
+        "plx_add_rms_drop_backward": [_P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _P, _P, _I, _P],
+        "plx_dropout": [_P, _P, _L, _P, _P, _I, _P],
         "plx_partial_colsum_workspace": [_I, _I, _I],
         "plx_partial_colsum": [_P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P],
         "plx_rms_backward": [_P, _P, _P, _P, _P, _P, _L, _I, _P],

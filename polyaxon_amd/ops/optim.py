@@ -51,7 +51,8 @@ class _PinnedRing:
         ev = self.events[i]
         if ev is not None:
             ev.synchronize()
-        self.buf[i, : len(values)] = torch.tensor(values, dtype=torch.float32)
+        # an fp32 tensor is staged as it is: raw 32-bit words viewed as fp32 keep their bits (ops/dropout.py)
+        self.buf[i, : len(values)] = values if torch.is_tensor(values) else torch.tensor(values, dtype=torch.float32)
         dst.copy_(self.buf[i, : dst.numel()], non_blocking=True)
         ev = self.events[i] or torch.cuda.Event()
         ev.record(torch.cuda.current_stream(dst.device))

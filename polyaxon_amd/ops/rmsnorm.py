@@ -1,5 +1,6 @@
 """RMSNorm and LayerNorm: fused HIP kernels (csrc/rmsnorm.hip) for bf16 CUDA tensors (bf16 in and out, fp32
-statistics and parameters), PyTorch composition otherwise."""
+statistics and parameters), PyTorch composition otherwise.  The fused add + norm pairs also carry residual dropout
+(``drop=``, ops/dropout.py), and :func:`dropout` is its standalone pass."""
 from __future__ import annotations
 
 import os
@@ -65,6 +66,68 @@ def _param_grads(parts, params, d: int):
     else:
         reduce()
     return [r if r is None else r.to(p.dtype) for r, p in zip(ret, params)]
+
+
+# ------------------------------------------------------------------------------------------ residual dropout
+def _drop_args(state, site):
+    return state.hp.data_ptr(), state.step_counter.data_ptr(), int(site)
+
+
+def _drop_supported(x: torch.Tensor) -> bool:
+    return x.is_cuda and x.dtype == torch.bfloat16 and x.numel() > 0 and x.numel() % 8 == 0 and x.is_contiguous()
+
+
+def _drop_launch(x: torch.Tensor, state, site) -> torch.Tensor:
+    y = torch.empty_like(x)
+    _native.check(_native.lib("plx_rms").plx_dropout(x.data_ptr(), y.data_ptr(), x.numel() // 8,
+                                                     *_drop_args(state, site), _stream()), "plx_dropout")
+    return y
+
+
+def _drop_grad(g, state, site):
+    """The gradient of a dropped-out branch from the gradient ``g`` of its output (None stays None)."""
+    if g is None:
+        return None
+    return _drop_launch(g.contiguous(), state, site)
+
+
+class _Dropout(torch.autograd.Function):
+    """y = keep ? c * x : 0 (csrc/rmsnorm.hip plx_dropout); the backward is the same kernel on dy at the same step."""
+
+    @staticmethod
+    def forward(ctx, x, state, site):
+        ctx.drop = (state, site)
+        return _drop_launch(x, state, site)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return _drop_launch(dy.contiguous().to(torch.bfloat16), *ctx.drop), None, None
+
+
+def drop_factor(like: torch.Tensor, state, site) -> torch.Tensor:
+    """fp32, shaped like ``like``: c where the element is kept, 0 where it is dropped -- the kernels' mask from its
+    numpy twin (ops/dropout.py mask_reference) at the step the device counter holds now (one host read of it)."""
+    from polyaxon_amd.ops import dropout as _drop
+
+    n = like.numel()
+    keep = _drop.mask_reference(state.key, state.step(), int(site), (n + 7) // 8, state.T).reshape(-1)[:n]
+    return torch.from_numpy(keep.astype("float32")).to(like.device).view(like.shape) * state.c
+
+
+def dropout(x: torch.Tensor, state, site: int) -> torch.Tensor:
+    """Dropout of site ``site`` of ``state`` (ops/dropout.py DropoutState): the HIP pass for contiguous bf16 GPU
+    tensors of a multiple of 8 elements, the same formula in torch with the same mask otherwise."""
+    if _drop_supported(x):
+        return _Dropout.apply(x, state, site)
+    return (x.float() * drop_factor(x, state, site)).to(x.dtype)
+
+
+def _drop_add_reference(x: torch.Tensor, res: torch.Tensor, state, site) -> torch.Tensor:
+    """s = x + drop(res) where the fused kernels do not apply: the standalone pass and a separate add on the GPU, the
+    contract's one-rounding formula in torch otherwise."""
+    if _drop_supported(res) and res.dtype == x.dtype:
+        return x + _Dropout.apply(res, state, site)
+    return (x.float() + drop_factor(res, state, site) * res.float()).to(x.dtype)
 
 
 class _RMSNorm(torch.autograd.Function):
@@ -139,10 +202,56 @@ class _AddRMSNorm(torch.autograd.Function):
         return dx, dx, _param_grads([part], [ctx.param], d)[0], None
 
 
-def add_rms_norm(x: torch.Tensor, res: torch.Tensor, weight: torch.Tensor, eps: float = 1e-5):
+class _AddRMSNormDrop(torch.autograd.Function):
+    """:class:`_AddRMSNorm` with residual dropout on ``res`` (csrc/rmsnorm.hip plx_add_rms_drop_*): s = x + drop(res);
+    the backward regenerates the mask from the step counter and returns dx for x and its dropped-out copy for res."""
+
+    @staticmethod
+    def forward(ctx, x, res, weight, eps, state, site):
+        ctx.set_materialize_grads(False)
+        lib = _native.lib("plx_rms")
+        d = x.shape[-1]
+        rows = x.numel() // d
+        s, y = torch.empty_like(x), torch.empty_like(x)
+        rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
+        w = weight.float().contiguous()
+        _native.check(lib.plx_add_rms_drop_forward(x.data_ptr(), res.data_ptr(), w.data_ptr(), s.data_ptr(),
+                                                   y.data_ptr(), rstd.data_ptr(), rows, d, float(eps),
+                                                   *_drop_args(state, site), _stream()), "plx_add_rms_drop_forward")
+        ctx.save_for_backward(s, w, rstd)
+        ctx.param, ctx.drop = weight, (state, site)
+        return s, y
+
+    @staticmethod
+    def backward(ctx, ds, dy):
+        lib = _native.lib("plx_rms")
+        s, w, rstd = ctx.saved_tensors
+        if dy is None:
+            return ds, _drop_grad(ds, *ctx.drop), None, None, None, None
+        d = s.shape[-1]
+        rows = s.numel() // d
+        dy = dy.contiguous().to(s.dtype)
+        ds = None if ds is None else ds.contiguous().to(s.dtype)
+        dx, dres = torch.empty_like(s), torch.empty_like(s)
+        part = torch.empty((lib.plx_rms_bwd_blocks(rows), d), dtype=torch.float32, device=s.device)
+        _native.check(lib.plx_add_rms_drop_backward(s.data_ptr(), w.data_ptr(), dy.data_ptr(), rstd.data_ptr(),
+                                                    None if ds is None else ds.data_ptr(), dx.data_ptr(),
+                                                    dres.data_ptr(), part.data_ptr(), rows, d, *_drop_args(*ctx.drop),
+                                                    _stream()), "plx_add_rms_drop_backward")
+        return dx, dres, _param_grads([part], [ctx.param], d)[0], None, None, None
+
+
+def add_rms_norm(x: torch.Tensor, res: torch.Tensor, weight: torch.Tensor, eps: float = 1e-5, drop=None):
     """(s, y) = (x + res, RMSNorm(s)): the pre-norm residual add fused into the next RMSNorm for bf16 GPU rows; the
-    separate add and :func:`rms_norm` otherwise."""
-    if supported(x) and res.dtype == x.dtype and res.shape == x.shape and x.is_contiguous() and res.is_contiguous():
+    separate add and :func:`rms_norm` otherwise.  ``drop = (state, site)``: residual dropout on ``res`` first
+    (ops/dropout.py), inside the same kernels."""
+    fused = supported(x) and res.dtype == x.dtype and res.shape == x.shape and x.is_contiguous() and res.is_contiguous()
+    if drop is not None:
+        if fused:
+            return _AddRMSNormDrop.apply(x, res, weight, eps, *drop)
+        s = _drop_add_reference(x, res, *drop)
+        return s, rms_norm(s, weight, eps)
+    if fused:
         return _AddRMSNorm.apply(x, res, weight, eps)
     s = x + res
     return s, rms_norm(s, weight, eps)
@@ -260,12 +369,64 @@ class _AddLayerNorm(torch.autograd.Function):
         return dx, dx, dw, db, None
 
 
+class _AddLayerNormDrop(torch.autograd.Function):
+    """:class:`_AddLayerNorm` with residual dropout on ``res`` (csrc/rmsnorm.hip plx_add_ln_drop_*): s = x + drop(res);
+    the backward regenerates the mask from the step counter and returns dx for x and its dropped-out copy for res."""
+
+    @staticmethod
+    def forward(ctx, x, res, weight, bias, eps, state, site):
+        ctx.set_materialize_grads(False)
+        lib = _native.lib("plx_rms")
+        d = x.shape[-1]
+        rows = x.numel() // d
+        s, y = torch.empty_like(x), torch.empty_like(x)
+        mean = torch.empty(rows, dtype=torch.float32, device=x.device)
+        rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
+        w, b = weight.float().contiguous(), bias.float().contiguous()
+        _native.check(lib.plx_add_ln_drop_forward(x.data_ptr(), res.data_ptr(), w.data_ptr(), b.data_ptr(),
+                                                  s.data_ptr(), y.data_ptr(), mean.data_ptr(), rstd.data_ptr(), rows, d,
+                                                  float(eps), *_drop_args(state, site), _stream()),
+                      "plx_add_ln_drop_forward")
+        ctx.save_for_backward(s, w, mean, rstd)
+        ctx.params, ctx.drop = (weight, bias), (state, site)
+        return s, y
+
+    @staticmethod
+    def backward(ctx, ds, dy):
+        lib = _native.lib("plx_rms")
+        s, w, mean, rstd = ctx.saved_tensors
+        d = s.shape[-1]
+        rows = s.numel() // d
+        if dy is None:  # only the residual stream is used downstream
+            return ds, _drop_grad(ds, *ctx.drop), None, None, None, None, None
+        dy = dy.contiguous().to(s.dtype)
+        ds = None if ds is None else ds.contiguous().to(s.dtype)
+        dx, dres = torch.empty_like(s), torch.empty_like(s)
+        nb = lib.plx_ln_bwd_blocks(rows, d)
+        part = torch.empty((2, nb, d), dtype=torch.float32, device=s.device)
+        _native.check(lib.plx_add_ln_drop_backward(s.data_ptr(), w.data_ptr(), dy.data_ptr(), mean.data_ptr(),
+                                                   rstd.data_ptr(), None if ds is None else ds.data_ptr(),
+                                                   dx.data_ptr(), dres.data_ptr(), part[0].data_ptr(),
+                                                   part[1].data_ptr(), rows, d, *_drop_args(*ctx.drop), _stream()),
+                      "plx_add_ln_drop_backward")
+        dw, db = _param_grads([part[0], part[1]], list(ctx.params), d)
+        return dx, dres, dw, db, None, None, None
+
+
 def add_layer_norm(x: torch.Tensor, res: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor,
-                   eps: float = 1e-5):
+                   eps: float = 1e-5, drop=None):
     """(s, y) = (x + res, LayerNorm(s)): the pre-norm transformer's residual add fused into the next norm for bf16 GPU
-    rows of d <= 1024 (one wave per row); the separate add and :func:`layer_norm` otherwise."""
-    if (supported(x) and res.dtype == x.dtype and res.shape == x.shape and x.shape[-1] <= 1024 and x.is_contiguous()
-            and res.is_contiguous()):
+    rows of d <= 1024 (one wave per row); the separate add and :func:`layer_norm` otherwise.  ``drop = (state, site)``:
+    residual dropout on ``res`` first (ops/dropout.py) -- inside the same kernels where they apply, the standalone
+    :func:`dropout` pass before the separate add above d = 1024."""
+    fused = (supported(x) and res.dtype == x.dtype and res.shape == x.shape and x.shape[-1] <= 1024
+             and x.is_contiguous() and res.is_contiguous())
+    if drop is not None:
+        if fused:
+            return _AddLayerNormDrop.apply(x, res, weight, bias, eps, *drop)
+        s = _drop_add_reference(x, res, *drop)
+        return s, layer_norm(s, weight, bias, eps)
+    if fused:
         return _AddLayerNorm.apply(x, res, weight, bias, eps)
     s = x + res
     return s, layer_norm(s, weight, bias, eps)

@@ -52,7 +52,7 @@ class ResidentTrialExecutor:
                  amp_dtype: Optional[torch.dtype] = torch.bfloat16, channels_last: bool = True,
                  ring_size: int = 4096, init_spec: Optional[Callable] = None,
                  lp_dtype: Optional[torch.dtype] = None, clip_grad: bool = False, lr_schedule=False,
-                 loss_hparams: bool = False):
+                 loss_hparams: bool = False, dropout: bool = False, dropout_seed: int = 0):
         """``lp_dtype`` (the language models, GPU): the model computes from bf16 weights with bf16 gradients and the
         optimizer keeps the fp32 master (ops/flat.py lp mode); every re-init / restore refreshes the bf16 copy.
         ``clip_grad``: global-norm gradient clipping (ops/optim.py) with ``max_grad_norm`` as one more device
@@ -65,7 +65,12 @@ class ResidentTrialExecutor:
         ``loss_hparams``: label smoothing and z-loss as two more device hyper-parameters (ops/loss_hp.py): the default
         loss reads them from device memory inside its fused kernels, a ``loss_fn`` is called as
         ``loss_fn(out, y, loss_hp=...)``; both start at 0 -- bitwise the plain loss -- until a trial sets them.  The
-        metric ring then records the plain NLL instead of the training loss (:meth:`_record`)."""
+        metric ring then records the plain NLL instead of the training loss (:meth:`_record`).
+        ``dropout``: residual dropout with its rate as one more device hyper-parameter (ops/dropout.py): the model's
+        ``set_dropout`` gets a state built on this executor's step counter, so the captured step draws fresh masks
+        every replay and its backward regenerates them; the rate starts at 0 -- bitwise the plain step -- until a
+        trial sets one.  ``dropout_seed`` keys the masks (not the trial's init seed: every trial sees the same
+        masks, and a restored snapshot continues the stream from its step counter alone)."""
         self.device = torch.device(device)
         self.is_cuda = self.device.type == "cuda"
         if channels_last:
@@ -84,6 +89,16 @@ class ResidentTrialExecutor:
             self.opt = FusedAdamW(self.flat, step_counter=self.step, max_grad_norm=clip, lr_schedule=sched)
         else:
             raise ValueError(f"unknown optimizer {optimizer!r}")
+        # off: nothing exists -- no tensor, the plain launches, and set_hparams drops the key
+        self.dropout = None
+        if dropout:
+            if not hasattr(model, "set_dropout"):
+                raise ValueError(f"dropout=True needs a model with set_dropout(); {type(model).__name__} has no "
+                                 "dropout sites")
+            from polyaxon_amd.ops.dropout import DropoutState
+
+            self.dropout = DropoutState(self.device, self.step, seed=dropout_seed)
+            model.set_dropout(self.dropout)
         # default: cross entropy of the fp32-cast logits; on the GPU in one fused HIP kernel each way (ops/lm.py
         # class_xent: no fp32 logits copy, log-softmax or NLL kernels between the head GEMM and its backward, where the
         # host launching them was the bottleneck of the forward -> backward hand-off; +0.1-0.2 %, r5_class_xent_ab.jsonl)
@@ -151,6 +166,10 @@ class ResidentTrialExecutor:
         from polyaxon_amd.parallel.ddp import FlatDDP
 
         self.ddp = FlatDDP(self.flat, process_group=process_group, bucket_mb=bucket_mb)
+        if self.dropout is not None:  # every rank of the gang draws its own masks
+            import torch.distributed as dist
+
+            self.dropout.set_rank(dist.get_rank(process_group))
         self.use_graph = False
         self._prefetch = False
 
@@ -328,6 +347,8 @@ class ResidentTrialExecutor:
             own = {k: v for k, v in hp.items() if k in KEYS}
             if own:
                 self.loss_hp.set(**own)
+        if self.dropout is not None and "dropout" in hp:
+            self.dropout.set(dropout=hp["dropout"])
         self.opt.set_hparams(**{k: v for k, v in hp.items() if k in self.opt.HP})
 
     def grad_norm(self) -> torch.Tensor:

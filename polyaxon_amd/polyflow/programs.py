@@ -23,6 +23,12 @@ Every built-in program also takes ``params: {loss_hparams: true}``: ``label_smoo
 hyper-parameters of the loss (ops/loss_hp.py), read from device memory by the fused cross-entropy kernels, both 0
 until a trial sets them.  The metric the program commits is then the plain NLL, not the training loss, so trials
 with different smoothing stay comparable.
+
+``gpt2`` and ``gpt2_tiny`` also take ``params: {dropout: true, dropout_seed: n}``: residual and embedding dropout
+(ops/dropout.py) with the rate ``dropout`` as a per-trial hyper-parameter, 0 until a trial sets it.  The rate is
+device data and no mask is stored: the step's kernels draw it from the device step counter, so one captured step
+serves every rate and draws fresh masks every replay.  ``dropout_seed`` keys the masks for the whole program, so
+trials differ by their weights and rates, not by their masks.  The other programs have no dropout sites and reject it.
 """
 from __future__ import annotations
 
@@ -67,6 +73,10 @@ class TrialProgram:
                 from polyaxon_amd.ops import loss_hp
 
                 ex.set_hparams(**loss_hp.DEFAULTS)
+            if self.info.get("dropout"):  # back from the warm-up's rate to none
+                from polyaxon_amd.ops import dropout
+
+                ex.set_hparams(**dropout.DEFAULTS)
         if ex.is_cuda:
             torch.cuda.synchronize(ex.device)
 
@@ -97,6 +107,26 @@ def _with_loss_hp(prog: TrialProgram, on: bool) -> TrialProgram:
         prog.hp_keys = prog.hp_keys + loss_hp.KEYS
         prog.info["warm_hparams"] = {**prog.info.get("warm_hparams", {}), "label_smoothing": 0.1, "z_loss": 1e-4}
         prog.info["loss_hparams"] = True
+    return prog
+
+
+def _dropout(params: Dict[str, Any]) -> bool:
+    return bool(params.get("dropout", False))
+
+
+def _no_dropout(name: str, params: Dict[str, Any]) -> None:
+    if _dropout(params) or "dropout_seed" in params:
+        raise ValueError(f"program {name} has no dropout sites: `dropout` is a param of gpt2 / gpt2_tiny only")
+
+
+def _with_dropout(prog: TrialProgram, on: bool) -> TrialProgram:
+    """``dropout`` programs understand the ``dropout`` rate and warm up at 0.1, so the warm steps draw masks."""
+    if on:
+        from polyaxon_amd.ops import dropout
+
+        prog.hp_keys = prog.hp_keys + dropout.KEYS
+        prog.info["warm_hparams"] = {**prog.info.get("warm_hparams", {}), "dropout": 0.1}
+        prog.info["dropout"] = True
     return prog
 
 
@@ -140,6 +170,7 @@ def _resnet(params: Dict[str, Any], device, tiny: bool) -> TrialProgram:
     from polyaxon_amd.ops.synth import SyntheticImages
     from polyaxon_amd.polyflow.executor import ResidentTrialExecutor
 
+    _no_dropout("resnet_tiny" if tiny else "resnet50", params)
     dev = torch.device(device)
     batch = int(params.get("batch", 8 if tiny else 256))
     image = int(params.get("image", 32 if tiny else 224))
@@ -167,6 +198,7 @@ def _mlp(params: Dict[str, Any], device) -> TrialProgram:
     from polyaxon_amd.polyflow.executor import ResidentTrialExecutor
     from polyaxon_amd.trainers import MLP
 
+    _no_dropout("mlp", params)
     dev = torch.device(device)
     bs = int(params.get("batch", 256))
     g = torch.Generator().manual_seed(int(params.get("data_seed", 0)))
@@ -219,8 +251,9 @@ def _gpt2(params: Dict[str, Any], device, tiny: bool) -> TrialProgram:
     ex = ResidentTrialExecutor(model, data, dev, loss_fn=loss_fn, optimizer="adamw",
                                use_graph=bool(params.get("graph", False)), channels_last=False,
                                lp_dtype=torch.bfloat16, clip_grad=clip, lr_schedule=_lr_schedule(params),
-                               loss_hparams=loss_hp)
-    return _with_loss_hp(_with_schedule(_with_clip(TrialProgram(
+                               loss_hparams=loss_hp, dropout=_dropout(params),
+                               dropout_seed=int(params.get("dropout_seed", 0)))
+    return _with_dropout(_with_loss_hp(_with_schedule(_with_clip(TrialProgram(
         ex, unit_steps=int(params.get("unit_steps", 4 if tiny else 10)),
         window=int(params.get("window", 4)),
         hp_keys=("lr", "beta1", "beta2", "eps", "weight_decay"),
@@ -230,7 +263,7 @@ def _gpt2(params: Dict[str, Any], device, tiny: bool) -> TrialProgram:
                                "weight_decay": 0.1},
               "tokens_per_step": batch * seq, "floor_loss": data.floor_loss,
               "unigram_loss": data.unigram_loss, "chance_loss": data.chance_loss,
-              "active_vocab": data.active_vocab}), clip), params), loss_hp)
+              "active_vocab": data.active_vocab}), clip), params), loss_hp), _dropout(params))
 
 
 PROGRAMS: Dict[str, Callable[[Dict[str, Any], Any], TrialProgram]] = {

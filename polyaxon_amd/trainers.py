@@ -244,6 +244,9 @@ def train_lm(argv=None) -> float:
     ap.add_argument("--zero1", action="store_true",
                     help="ZeRO-1: reduce-scatter each gradient bucket, AdamW on this rank's 1/W slice inside the "
                          "backward, all-gather the bf16 weights (parallel/ddp.py); also PLX_ZERO1=1")
+    ap.add_argument("--dropout", type=float, default=0.0,
+                    help="residual and embedding dropout rate (ops/dropout.py: device data, masks regenerated in the "
+                         "backward from the step counter); 0: no dropout state, the plain launches")
     _schedule_args(ap, warmup=False)  # --warmup_steps above: host-side without a schedule, the schedule's with one
     _loss_args(ap)
     args = _parse(ap, argv)
@@ -301,6 +304,14 @@ def train_lm(argv=None) -> float:
 
         loss_hp = LossHParams(dev)
         loss_hp.set(label_smoothing=args.label_smoothing, z_loss=args.z_loss)
+    if args.dropout != 0:  # device data of the dropout sites; 0: not built at all
+        from polyaxon_amd.ops.dropout import DropoutState
+
+        # the masks of a step are drawn from `step`, which moves only after the optimizer step below: the backward
+        # regenerates the forward's masks
+        drop = DropoutState(dev, step, rank=info["rank"])
+        drop.set(dropout=args.dropout)
+        model.set_dropout(drop)
     metrics = MetricReducer(dev, force_comm=force)  # cross-rank mean of the logged loss (RCCL communicator, GPU)
     g = torch.Generator(device=dev).manual_seed(args.seed + 1000 * info["rank"])
 
