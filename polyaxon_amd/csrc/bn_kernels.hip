@@ -1248,7 +1248,7 @@ struct BnBackwardArgs {
   float *dgamma, *dbeta, *coef /* [3C] */, *workspace;
   const float* ext_part;
   int ext_nblk, accumulate;  // accumulate: dgamma / dbeta += (else =)
-  ResBn resbn;            // all null: none; else needs dres
+  ResBn resbn;            // all null: none; else needs dres and C <= 2048
   unsigned* counters;
 };
 
@@ -1289,6 +1289,9 @@ PLX_API int plx_bn_backward(const BnBackwardArgs* a, hipStream_t stream) {
                  rb.invstd == nullptr))
     return 1;
   if (a->dx == nullptr && (a->dres != nullptr || has_rb)) return 1;
+  // the dx pass sums a ResBn's partials over the threads of ONE block that share a channel group: above kBlock groups
+  // (C > 2048) a block holds only kBlock of the G groups of a row of `part` and would leave the others unwritten
+  if (has_rb && p.G > kBlock) return 1;
   const bool own = a->ext_part == nullptr;  // this call runs the reduce pass itself
   const int nblk = own ? p.nblk : a->ext_nblk;
   float* l2 = own ? a->workspace + 2 * (int64_t)nblk * C : a->workspace;

@@ -149,8 +149,9 @@ class _BNAct(torch.autograd.Function):
                 link.affine = stats[2 * c:]
         # rlink: the residual came from a fused BatchNorm whose output nothing else consumes (a downsampling branch):
         # d_residual is that BatchNorm's whole gradient, so the dx pass below reduces its backward partials too
+        # (c <= 2048: plx_bn_backward refuses a ResBn above 256 channel groups; that BatchNorm then runs its own reduce)
         ctx.rlink = rlink if (rlink is not None and residual is not None and rlink.x is not None
-                              and rlink.x.shape == x.shape and ctx.box is None) else None
+                              and rlink.x.shape == x.shape and ctx.box is None and c <= 2048) else None
         if defer:
             return x.view_as(x)  # the raw input; bn_act marks it _plx_deferred
         return y

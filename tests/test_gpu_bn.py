@@ -289,6 +289,7 @@ def test_bn_refused_calls_launch_nothing(cuda):
         (bn_backward, dict(bwd, dx=None, dres=dres)),                    # no dx pass, but something for it to write
         (bn_backward, dict(bwd, dx=None, dres=dres, resbn=resbn)),
         (bn_backward, dict(bwd, dx=None, resbn=resbn, **ext)),
+        (bn_backward, dict(bwd, c=4096, dres=dres, resbn=resbn)),        # a ResBn above 256 channel groups
     ]
     for fn, kw in refused:
         with pytest.raises(RuntimeError, match="failed with code"):
