@@ -16,9 +16,9 @@
 //   bn_apply_kernel                y = act(x*scale + bias [+ res]), and the 1-bit ReLU mask
 //   bn_bwd_reduce_kernel           partial sums of dz and dz*xhat   (dz = dy * [y > 0] when act)
 //   bn_bwd_reduce_finalize_kernel  level-2 reduce, then dgamma, dbeta and the dx coefficients  dx = A*dz + B*x + D
-//   bn_bwd_dx_kernel               dx (and d_residual = dz) in one pass, optionally with the reduction partials of the
-//                                  BatchNorm that produced the residual (ResBn: a downsampling branch's BN skips its
-//                                  reduce)
+//   bn_bwd_dx_kernel               dx (and d_residual = dz where asked for) in one pass, optionally with the reduction
+//                                  partials of the BatchNorm that produced the residual (ResBn: a downsampling
+//                                  branch's BN skips its reduce)
 //   (without a counter array a reduce + finalize is bn_partial_reduce_kernel + bn_{fwd,bwd}_finalize_kernel)
 // Entry points: plx_bn_forward / plx_bn_backward (one argument struct each), plx_bn_apply, plx_bn_apply_res_relu, the
 // stem's plx_stem_bn_pool_forward / _backward (stem_*_kernel), and the size queries (plx_bn_workspace, ...).
@@ -26,6 +26,7 @@
 
 #include "handoff.h"
 #include <stdint.h>
+#include <type_traits>
 
 #define PLX_API extern "C" __attribute__((visibility("default")))
 
@@ -525,7 +526,9 @@ struct ResBn {
 // RP: also reduce the residual BatchNorm's partials (ResBn).  A separate instantiation: its extra state
 // (90 VGPRs) would cut the plain pass from 8 to 5 waves per SIMD, and this memory-bound pass needs them.
 // RMASK (RP only): the residual BatchNorm had a ReLU (rb.mask set) -- compile-time, no per-trip pointer test
-template <bool RP, bool RELU, bool RMASK = false>
+// DRES: d_residual = dz is stored (dres set) -- compile-time too: a consumer that takes (dy, mask) instead of dz
+// (the downsample BatchNorm behind a ResBn, plx_gemm_nt_bndx) leaves the pass without the store and its pointer test
+template <bool RP, bool RELU, bool RMASK, bool DRES>
 __global__ __launch_bounds__(kBlock) void bn_bwd_dx_kernel(const bf16x8* __restrict__ x, const uint8_t* __restrict__ mask,
                                                            const bf16x8* __restrict__ dy, bf16x8* __restrict__ dx,
                                                            bf16x8* __restrict__ dres, const float* __restrict__ coef,
@@ -556,7 +559,7 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_dx_kernel(const bf16x8* __restr
 #pragma unroll
       for (int k = 0; k < 8; ++k) g[k] = (mb >> k) & 1u ? g[k] : 0.f;
     }
-    if (dres != nullptr) store8(dres + i, g);
+    if constexpr (DRES) store8(dres + i, g);
     if constexpr (rp) {
       float x2[8];
       load8(rb.x + i, x2);
@@ -640,9 +643,15 @@ inline int apply_grid(int64_t n_vec, int G) {
 inline void launch_dx(hipStream_t stream, int64_t n_vec, int G, const void* x, const uint8_t* mask, const void* dy,
                       void* dx, void* dres, const float* coef, int relu, const ResBn& rb) {
   const dim3 grid(apply_grid(n_vec, G));
-  auto k = rb.part == nullptr ? (relu ? bn_bwd_dx_kernel<false, true> : bn_bwd_dx_kernel<false, false>)
-           : rb.mask != nullptr ? (relu ? bn_bwd_dx_kernel<true, true, true> : bn_bwd_dx_kernel<true, false, true>)
-                                : (relu ? bn_bwd_dx_kernel<true, true> : bn_bwd_dx_kernel<true, false>);
+  auto pick = [&](auto d) {
+    constexpr bool DRES = decltype(d)::value;
+    return rb.part == nullptr
+               ? (relu ? bn_bwd_dx_kernel<false, true, false, DRES> : bn_bwd_dx_kernel<false, false, false, DRES>)
+           : rb.mask != nullptr
+               ? (relu ? bn_bwd_dx_kernel<true, true, true, DRES> : bn_bwd_dx_kernel<true, false, true, DRES>)
+               : (relu ? bn_bwd_dx_kernel<true, true, false, DRES> : bn_bwd_dx_kernel<true, false, false, DRES>);
+  };
+  auto k = dres != nullptr ? pick(std::true_type{}) : pick(std::false_type{});
   hipLaunchKernelGGL(k, grid, dim3(kBlock), 0, stream, (const bf16x8*)x, mask, (const bf16x8*)dy, (bf16x8*)dx,
                      (bf16x8*)dres, coef, n_vec, G, relu, rb);
 }
@@ -1237,7 +1246,9 @@ struct BnForwardArgs {
 
 struct BnBackwardArgs {
   const void* x;
-  const uint8_t* mask;    // the forward's ReLU bit mask: required when relu and a pass reads it
+  const uint8_t* mask;    // the ReLU bit mask dz = dy * mask is formed with: required when relu and a pass reads it.
+                          // The forward's own, or a foreign one: that of the ReLU downstream whose incoming gradient dy
+                          // is (a downsample BatchNorm behind bn3's add + ReLU, handed bn3's dy instead of d_residual)
   const void* dy;
   void* dx;               // nullptr: reduce + finalize only (dgamma, dbeta, coef): dx = coef[0] * dz + coef[1] * x +
                           // coef[2] is then formed by the data-gradient GEMM that consumes it (plx_gemm_nt_bndx)
@@ -1248,8 +1259,10 @@ struct BnBackwardArgs {
   float *dgamma, *dbeta, *coef /* [3C] */, *workspace;
   const float* ext_part;
   int ext_nblk, accumulate;  // accumulate: dgamma / dbeta += (else =)
-  ResBn resbn;            // all null: none; else needs dres and C <= 2048
+  ResBn resbn;            // all null: none; else needs dx, C <= 2048, and dres unless no_dres
   unsigned* counters;
+  int no_dres;            // 1: the caller states that d_residual's consumer takes (dy, mask) instead of dz, so a ResBn
+                          // comes without dres (0: a ResBn without dres is a forgotten buffer and is refused)
 };
 
 PLX_API int plx_bn_args_size(int backward) {
@@ -1285,9 +1298,11 @@ PLX_API int plx_bn_backward(const BnBackwardArgs* a, hipStream_t stream) {
   if (!plan_for(a->M, C, &p) || (a->ext_part != nullptr && a->ext_nblk < 1)) return 1;
   // the reduce and the dx pass read the mask; with external partials and no dx pass nothing does
   if (relu && a->mask == nullptr && (a->ext_part == nullptr || a->dx != nullptr)) return 1;
-  if (has_rb && (a->dres == nullptr || rb.part == nullptr || rb.x == nullptr || rb.mean == nullptr ||
-                 rb.invstd == nullptr))
-    return 1;
+  // a ResBn needs the dx pass (below); dres too, unless the caller states that d_residual's consumer takes (dy, mask)
+  // instead of dz (no_dres) -- and then passing one is a contradiction
+  if (has_rb && (rb.part == nullptr || rb.x == nullptr || rb.mean == nullptr || rb.invstd == nullptr)) return 1;
+  if (has_rb && (a->dres == nullptr) != (a->no_dres != 0)) return 1;
+  if (!has_rb && a->no_dres) return 1;
   if (a->dx == nullptr && (a->dres != nullptr || has_rb)) return 1;
   // the dx pass sums a ResBn's partials over the threads of ONE block that share a channel group: above kBlock groups
   // (C > 2048) a block holds only kBlock of the G groups of a row of `part` and would leave the others unwritten

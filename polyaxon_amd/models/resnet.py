@@ -50,7 +50,9 @@ class Bottleneck(nn.Module):
             out = self.bn2(self.conv2(out, bn_link=True))
             return self.bn3(self.conv3(out, bn_link=True), x, residual_grad_box=box, defer_res_relu=defer_out)
         # downsampling block: conv1's data gradient is deferred into the downsample conv's dgrad epilogue, and the
-        # downsample BatchNorm's output feeds only bn3, so bn3's dx pass reduces that BatchNorm's backward partials
+        # downsample BatchNorm's output feeds only bn3, so bn3's backward hands it (dy, mask3) instead of writing
+        # d_residual, and either reduces that BatchNorm's backward partials in its dx pass or, where conv3's data
+        # gradient forms bn3's dx, leaves them to that BatchNorm's own reduce (ops.conv1x1.ds_bwd_route)
         identity = self.downsample(x, grad_box=box)
         out = self.bn1(self.conv1(x, grad_sink=box, bn_link=True))
         out = self.bn2(self.conv2(out, bn_link=True))

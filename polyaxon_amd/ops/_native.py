@@ -422,7 +422,7 @@ class BnBackwardArgs(ctypes.Structure):
     _fields_ = [("x", _P), ("mask", _P), ("dy", _P), ("dx", _P), ("dres", _P), ("M", _L), ("C", _I), ("relu", _I),
                 ("gamma", _P), ("save_mean", _P), ("save_invstd", _P), ("dgamma", _P), ("dbeta", _P), ("coef", _P),
                 ("workspace", _P), ("ext_part", _P), ("ext_nblk", _I), ("accumulate", _I), ("resbn", ResBnArgs),
-                ("counters", _P)]
+                ("counters", _P), ("no_dres", _I)]
 
 
 class GemmBnBwdArgs(ctypes.Structure):

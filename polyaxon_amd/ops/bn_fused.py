@@ -15,7 +15,7 @@ from typing import Optional
 import torch
 
 from polyaxon_amd.ops import _native
-from polyaxon_amd.ops.conv1x1 import BnLink, PendingApply, fill_pending
+from polyaxon_amd.ops.conv1x1 import BnLink, PendingApply, ds_bwd_route, fill_pending
 from polyaxon_amd.ops.flat import direct_grad
 
 
@@ -70,14 +70,15 @@ def bn_forward(*, x, m, c, gamma, beta, eps, momentum, save_mean, save_invstd, s
 
 def bn_backward(*, x, dy, m, c, gamma, save_mean, save_invstd, dgamma, dbeta, coef, workspace, mask=None, dx=None,
                 dres=None, relu=False, accumulate=0, ext_part=None, ext_nblk=0, resbn=None, counters=None,
-                stream=None) -> None:
+                stream=None, no_dres=False) -> None:
     """``plx_bn_backward`` (csrc/bn_kernels.hip ``BnBackwardArgs``); ``dx=None``: reduce + finalize only; ``resbn``:
-    a :class:`~polyaxon_amd.ops._native.ResBnArgs` or ``None``.  Raises when the library refuses the call."""
+    a :class:`~polyaxon_amd.ops._native.ResBnArgs` or ``None``; ``no_dres``: that ResBn comes without ``dres`` on
+    purpose (its consumer takes ``dy`` and the mask).  Raises when the library refuses the call."""
     a = _native.BnBackwardArgs(
         x=_p(x), mask=_p(mask), dy=_p(dy), dx=_p(dx), dres=_p(dres), M=m, C=c, relu=int(relu), gamma=_p(gamma),
         save_mean=_p(save_mean), save_invstd=_p(save_invstd), dgamma=_p(dgamma), dbeta=_p(dbeta), coef=_p(coef),
         workspace=_p(workspace), ext_part=_p(ext_part), ext_nblk=ext_nblk, accumulate=int(accumulate),
-        counters=_p(counters))
+        counters=_p(counters), no_dres=int(no_dres))
     if resbn is not None:
         a.resbn = resbn
     rc = _lib().plx_bn_backward(ctypes.byref(a), _stream() if stream is None else stream)
@@ -148,7 +149,8 @@ class _BNAct(torch.autograd.Function):
             if defer:
                 link.affine = stats[2 * c:]
         # rlink: the residual came from a fused BatchNorm whose output nothing else consumes (a downsampling branch):
-        # d_residual is that BatchNorm's whole gradient, so the dx pass below reduces its backward partials too
+        # d_residual is that BatchNorm's whole gradient, so the dx pass below reduces its backward partials too, or
+        # (ops.conv1x1.ds_bwd_route "A") leaves the reduce to it; either way it gets (dy, mask) instead of d_residual
         # (c <= 2048: plx_bn_backward refuses a ResBn above 256 channel groups; that BatchNorm then runs its own reduce)
         ctx.rlink = rlink if (rlink is not None and residual is not None and rlink.x is not None
                               and rlink.x.shape == x.shape and ctx.box is None and c <= 2048) else None
@@ -171,8 +173,25 @@ class _BNAct(torch.autograd.Function):
         # identity block: the residual's gradient dz = dy * mask is not written here; dy and the mask ride into
         # conv1's dgrad epilogue (GradMailbox.put_masked), which adds them
         masked_box = ctx.box is not None and ctx.relu and mask is not None
+        # downsampling block (rlink): the residual's gradient is not written either -- dy itself is returned for it and
+        # the downsample BatchNorm's backward forms dz = dy * mask from this ReLU's mask (BnLink.foreign), on route "A"
+        # or "B" of ops.conv1x1.ds_bwd_route; "off" writes d_residual
+        rl = ctx.rlink
+        route = "off"
+        # part: the consumer's dgrad epilogue already reduced dz and dz*xhat per block
+        part, nblk = ctx.link.take() if ctx.link is not None else (None, 0)
+        if rl is not None and ctx.relu and mask is not None and rl.mask is None:
+            sk = ctx.dxsink
+            route = ds_bwd_route(sk.cin if sk is not None else 0, c, sk is not None and part is not None)
+        # the mask test of a BatchNorm that is itself on the receiving end: dz = dy * (the ReLU mask downstream)
+        foreign, relu = (ctx.link.foreign if ctx.link is not None else None), ctx.relu
+        if foreign is not None:
+            ctx.link.foreign = None
+            if relu or foreign[0].data_ptr() != dy.data_ptr() or foreign[0].shape != dy.shape:
+                raise RuntimeError("BnLink.foreign: the gradient handed to the BatchNorm is not the one its mask masks")
+            relu, mask = True, foreign[1]
         dres = (torch.empty_like(x, memory_format=torch.channels_last)
-                if ctx.has_res and not masked_box else None)
+                if ctx.has_res and not masked_box and route == "off" else None)
         if ctx.direct is not None:
             dg_ptr, db_ptr, acc = ctx.direct[0].data_ptr(), ctx.direct[1].data_ptr(), 1
             dgb = None
@@ -180,23 +199,23 @@ class _BNAct(torch.autograd.Function):
             dgb = torch.empty(2 * c, **f32)
             dg_ptr, db_ptr, acc = dgb.data_ptr(), dgb[c:].data_ptr(), 0
         coef = torch.empty(3 * c, **f32)
-        # part: the consumer's dgrad epilogue already reduced dz and dz*xhat per block
-        part, nblk = ctx.link.take() if ctx.link is not None else (None, 0)
         # only dx to write (dxsink): reduce / finalize here, and the data-gradient GEMM of the convolution that produced
         # x forms dx = coef[0]·dz + coef[1]·x + coef[2] itself, into this (still unwritten) buffer
-        sink = ctx.dxsink if dres is None else None
+        sink = ctx.dxsink if (dres is None and route != "B") else None
         rb = None
-        if ctx.rlink is not None and dres is not None:
-            rl = ctx.rlink
+        if rl is not None and route != "A":  # the dx pass reduces the residual BatchNorm's partials, with or without dres
             rl.nblk = _native.size("plx_bn", "plx_bn_dx_blocks", m, c)
             rl.part = torch.empty(2 * rl.nblk * c, **f32)
             rb = _native.ResBnArgs(_p(rl.x), _p(rl.mask), _p(rl.mean), _p(rl.invstd), _p(rl.part))
         bn_backward(x=x, mask=mask, dy=dy, dx=None if sink is not None else dx, dres=dres, m=m, c=c, gamma=weight,
                     save_mean=stats, save_invstd=stats.data_ptr() + 4 * c, dgamma=dg_ptr, dbeta=db_ptr, coef=coef,
-                    workspace=_workspace(m, c, part, nblk, x.device), ext_part=part, ext_nblk=nblk, relu=ctx.relu,
-                    accumulate=acc, resbn=rb, counters=_counters(x.device))
+                    workspace=_workspace(m, c, part, nblk, x.device), ext_part=part, ext_nblk=nblk, relu=relu,
+                    accumulate=acc, resbn=rb, counters=_counters(x.device), no_dres=route == "B")
         if sink is not None:
-            sink.put(dy, x, mask if ctx.relu else None, coef, dx)
+            sink.put(dy, x, mask if relu else None, coef, dx)
+        if route != "off":  # the residual BatchNorm's backward gets dy itself and masks it with this ReLU's mask
+            rl.foreign = (dy, mask)
+            dres = dy
         if ctx.box is not None:  # the residual's gradient rides into conv1's dgrad epilogue (ops.conv1x1)
             if masked_box:
                 ctx.box.put_masked(dy, mask)
@@ -243,8 +262,9 @@ def bn_act(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, running_me
     """``ext_stats`` = (fp32 [2][nblk][C] channel sums / sums of squares of ``x``, nblk) from the op that
     produced ``x`` (the 1x1-conv GEMM epilogue); training mode then skips the stats pass.  ``residual_link``:
     ``residual`` is the output of a fused BatchNorm that nothing else consumes; its backward partials are then
-    reduced by this op's dx pass.  ``defer_apply`` (training, no activation, no residual): skip the apply pass
-    and return ``x`` itself marked ``_plx_deferred``; the fused BatchNorm that takes it as its residual applies
+    reduced by this op's dx pass, and with ``PLX_DS_BWD_FUSED`` (ops.conv1x1.ds_bwd_route) the backward writes no
+    d_residual: that BatchNorm gets this op's incoming gradient and ReLU mask.  ``defer_apply`` (training, no
+    activation, no residual): skip the apply pass and return ``x`` itself marked ``_plx_deferred``; the fused BatchNorm that takes it as its residual applies
     the scale/bias while adding (a ResNet downsampling branch: ~0.3 ms of a bs-256 step), any other consumer
     must call :func:`materialize` first.  ``dx_sink``: the :class:`~polyaxon_amd.ops.conv1x1.DxSink` the 1x1
     convolution that produced ``x`` attached to it; the backward then leaves its dx pass to that convolution's

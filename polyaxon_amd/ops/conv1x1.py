@@ -75,6 +75,43 @@ def dgrad_wgrad_fused_ok(cin: int, cout: int) -> bool:
             and bool(_native.lib("plx_conv").plx_get_tn_atomic()))
 
 
+# A/B knob, read once at load: a downsampling block's bn3 backward no longer writes d_residual = dy * mask3 -- the
+# downsample BatchNorm's backward takes (dy, mask3) instead (BnLink.foreign).  1 = route A (:func:`ds_bwd_route`) where
+# conv3's data gradient also forms its weight gradient (layer 1.0), route B elsewhere; 2 = route A wherever conv3 has a
+# dx sink (layer 2.0 too); 0 = the dx pass writes d_residual and the downsample BatchNorm reads it back
+_DS_BWD_FUSED = int(os.environ.get("PLX_DS_BWD_FUSED", "1") or 0)
+
+
+def set_ds_bwd_fused(mode: int) -> int:
+    """Set the downsampling blocks' backward mode (0, 1 or 2) for the backwards run from now on; returns the previous."""
+    global _DS_BWD_FUSED
+    prev, _DS_BWD_FUSED = _DS_BWD_FUSED, int(mode)
+    return prev
+
+
+def ds_bwd_route(cin: int, cout: int, has_sink: bool, mode: int = None, wgrad_fused: bool = None) -> str:
+    """How the backward of a downsampling block's bn3 (``cout`` channels, behind conv3 with ``cin`` inputs) hands the
+    residual's gradient to the downsample BatchNorm.
+
+    * ``"A"``: bn3 runs its reduce / finalize only; conv3's data-gradient GEMM forms bn3's dx (``has_sink``: conv3
+      attached a :class:`DxSink`, and the next block's conv1 reduced bn3's partials, so bn3 has no pass of its own
+      left), and the downsample BatchNorm runs its own reduce on (dy, mask3).  Taken where that
+      GEMM also forms conv3's weight gradient (``wgrad_fused``, default :func:`dgrad_wgrad_fused_ok`: layer 1.0 with
+      atomic weight gradients), so neither dx nor d_residual is stored; with mode 2 wherever conv3 has a sink.
+    * ``"B"``: bn3's dx pass stays and reduces the downsample BatchNorm's partials (ResBn) but writes no d_residual;
+      the downsample BatchNorm's dx reads (dy, mask3).
+    * ``"off"``: d_residual is written and read back -- mode 0, and above 2048 channels, where ``plx_bn_backward``
+      refuses a ResBn."""
+    mode = _DS_BWD_FUSED if mode is None else mode
+    if not mode or cout > 2048:
+        return "off"
+    if has_sink and mode >= 2:
+        return "A"
+    if has_sink and (dgrad_wgrad_fused_ok(cin, cout) if wgrad_fused is None else wgrad_fused):
+        return "A"
+    return "B"
+
+
 def _num_cus(dev: torch.device) -> int:
     idx = dev.index if dev.index is not None else torch.cuda.current_device()
     if idx not in _CUS:
@@ -330,10 +367,11 @@ class DxSink:
     payload, checks that the gradient it was handed is that very buffer, and its GEMM fills it on the way.  The
     payload keeps the operands alive until then."""
 
-    __slots__ = ("payload",)
+    __slots__ = ("payload", "cin", "cout")
 
-    def __init__(self):
+    def __init__(self, cin: int = 0, cout: int = 0):
         self.payload = None
+        self.cin, self.cout = cin, cout  # the convolution's channel counts (ds_bwd_route asks)
 
     def put(self, g: torch.Tensor, x: torch.Tensor, mask, coef: torch.Tensor, dx: torch.Tensor) -> None:
         self.payload = (g, x, mask, coef, dx)
@@ -348,10 +386,15 @@ def dx_sink_for(x: torch.Tensor, weight: torch.Tensor):
     K (= Cout) is at least twice its N (= Cin), and N fits one tile (N <= 128).  With two or four N tiles per row
     panel every tile's block repeats the loads and the transform; measured alone that ties (N = 256) or loses
     (N = 512) against the two kernels (profiles/bn_dx_fused.md), so those stay on them."""
-    if not _BN_DX_FUSED or not (torch.is_grad_enabled() and x.requires_grad):
+    if not (torch.is_grad_enabled() and x.requires_grad):
         return None
     cout, cin = weight.shape[0], weight.shape[1]
-    return DxSink() if (cout >= 2 * cin and cin <= 128) else None
+    return DxSink(cin, cout) if dx_sink_shape_ok(cin, cout) else None
+
+
+def dx_sink_shape_ok(cin: int, cout: int) -> bool:
+    """:func:`dx_sink_for`'s rule on the channel counts alone."""
+    return _BN_DX_FUSED and cout >= 2 * cin and cin <= 128
 
 
 class PendingApply:
@@ -427,10 +470,13 @@ class BnLink:
     (``bn_link=True``) ``request``s a partials buffer and its dgrad GEMM epilogue writes the per-block
     Σdz and Σdz·x̂ (csrc/conv_gemm.hip ``BnBwd``); the BatchNorm backward then skips its reduce pass."""
 
-    __slots__ = ("x", "mask", "mean", "invstd", "part", "nblk", "_args", "affine", "split")
+    __slots__ = ("x", "mask", "mean", "invstd", "part", "nblk", "_args", "affine", "split", "foreign")
 
     def __init__(self, x=None, mask=None, mean=None, invstd=None):
         self.x, self.mask, self.mean, self.invstd = x, mask, mean, invstd
+        # (dy, mask3): the gradient this BatchNorm's backward receives is bn3's incoming dy as is, and its dz is
+        # dy * mask3, the ReLU mask of bn3 downstream (a downsampling block with PLX_DS_BWD_FUSED: no d_residual)
+        self.foreign = None
         self.affine = None  # deferred apply: fp32 [scale | bias] the consumer applies to the raw x
         self.part = None
         self.nblk = 0
