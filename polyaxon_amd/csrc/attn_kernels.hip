@@ -26,6 +26,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #define PLX_API extern "C" __attribute__((visibility("default")))
 
@@ -54,6 +55,120 @@ struct AttnArgs {
   float scale;  // softmax_scale
   const __bf16* zero;  // >= 16 zero bytes
 };
+
+// ------------------------------------------------------------------------------------------ attention dropout
+// Dropout on the softmax probabilities, its rate device data (ops/attn_dropout.py AttnDropoutState): hp[0] the
+// threshold T = min(round(p * 256), 255), hp[1] the bits of the fp32 scale c = 256 / (256 - T) (1.0 exactly at T = 0),
+// hp[2..3] the Philox key; step[0] is the trainer's device step counter, read at run time, so a replayed graph draws
+// fresh masks every step and the three backward kernels regenerate the forward's mask instead of loading one.
+// Element (b, h, q, k) -- h the query head, q / k absolute indices -- of layer l draws
+//   w = Philox4x32-10(counter = (q >> 2, k >> 2, step, 0x80000000 | (l << 16) | (b * H + h)), key),
+// takes the byte (w[q & 3] >> 8 * (k & 3)) & 0xff and is kept iff byte >= T: one call covers a 4 x 4 block, whichever
+// way a kernel holds the scores and whatever its tiles are.  Valid for b * H + h < 65536 and l < 32768.
+// Math: the softmax statistics (m, l, lse2) use the undropped P; O = (c M o P) V; dP = c M o (dO V^T),
+// dS = P o (dP - delta), dV = (c M o P)^T dO, delta = rowsum(dO o O) as before.  c multiplies the finished O row, the
+// finished dV rows and dp before the subtraction; the mask zeroes the MFMA operand, never the scores.  At T = 0 no
+// bits are drawn and every product with c = 1.0 leaves the plain kernels' bits.
+struct AttnDropArgs {
+  AttnArgs a;
+  const uint32_t* hp;
+  const int32_t* step;
+  uint32_t layer;
+};
+
+template <bool DROP>
+using KArgs = std::conditional_t<DROP, AttnDropArgs, AttnArgs>;
+
+__host__ __device__ __forceinline__ const AttnArgs& attn_args(const AttnArgs& ka) { return ka; }
+__host__ __device__ __forceinline__ const AttnArgs& attn_args(const AttnDropArgs& ka) { return ka.a; }
+
+struct Drop {
+  uint32_t T, k0, k1, t, stream;
+  float c;
+};
+
+__device__ __forceinline__ Drop drop_load(const AttnDropArgs& ka, int bh) {
+  return Drop{ka.hp[0], ka.hp[2], ka.hp[3], (uint32_t)ka.step[0], 0x80000000u | (ka.layer << 16) | (uint32_t)bh,
+              __uint_as_float(ka.hp[1])};
+}
+
+// the four words of block (qb, kb) = (q >> 2, k >> 2)
+__device__ __forceinline__ void drop_block(const Drop& d, uint32_t qb, uint32_t kb, uint32_t (&c)[4]) {
+  c[0] = qb, c[1] = kb, c[2] = d.t, c[3] = d.stream;
+  uint32_t k0 = d.k0, k1 = d.k1;
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t lo0 = 0xD2511F53u * c[0], hi0 = __umulhi(0xD2511F53u, c[0]);
+    const uint32_t lo1 = 0xCD9E8D57u * c[2], hi1 = __umulhi(0xCD9E8D57u, c[2]);
+    c[0] = hi1 ^ c[1] ^ k0;
+    c[1] = lo1;
+    c[2] = hi0 ^ c[3] ^ k1;
+    c[3] = lo0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+}
+
+__device__ __forceinline__ bool drop_keep(const Drop& d, uint32_t word, int e) {
+  return ((word >> (8 * e)) & 0xffu) >= d.T;
+}
+
+// lane `SRC` of every quad of adjacent lanes broadcasts x to its quad (DPP quad_perm, no LDS)
+template <int SRC>
+__device__ __forceinline__ uint32_t quad_bcast(uint32_t x) {
+  return (uint32_t)__builtin_amdgcn_mov_dpp((int)x, SRC * 0x55, 0xf, 0xf, true);
+}
+
+// Sharing the draws.  The 4 lanes of a quad own 4 adjacent queries (forward / dQ) or 4 adjacent keys (dK/dV), so
+// every call one of them needs, all of them need: each lane evaluates a quarter of the quad's calls and the words
+// travel by quad broadcasts -- one Philox evaluation per 16 mask bytes per lane instead of one per 4.  Every lane of the
+// wave is active wherever these run (the skips around them are wave-uniform).
+
+// Forward / dQ orientation (S^T): this lane owns query q, registers 4g..4g+3 of score tile t are the 4 keys of block
+// kb0 + 8 t + 2 g (kb0 = (kv0 >> 2) + h) and need word q & 3 of that block's call; byte e belongs to register 4g + e.
+// Lane s = q & 3 of the quad evaluates calls j = 4 t + g = 2 s and 2 s + 1.
+template <int J>
+__device__ __forceinline__ uint32_t drop_gather_row(const Drop& d, const uint32_t (&w)[2][4], int s) {
+  const uint32_t b0 = quad_bcast<J / 2>(w[J & 1][0]), b1 = quad_bcast<J / 2>(w[J & 1][1]);
+  const uint32_t b2 = quad_bcast<J / 2>(w[J & 1][2]), b3 = quad_bcast<J / 2>(w[J & 1][3]);
+  const uint32_t word = s == 0 ? b0 : s == 1 ? b1 : s == 2 ? b2 : b3;
+  uint32_t keep = 0;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) keep |= (uint32_t)(((word >> (8 * e)) & 0xffu) >= d.T) << (4 * J + e);
+  return keep;
+}
+
+// The keep bits of this lane's query against one 64-key tile, drawn before the tile's MFMA chains so that the integer
+// work overlaps them and only one register lives through them: bit 16 t + r is register r of score tile t, i.e. key
+// kv0 + 32 t + acc_row(r, h).
+__device__ __forceinline__ uint32_t drop_keep_tile(const Drop& d, int q, int kb0) {
+  const int s = q & 3;
+  uint32_t w[2][4];
+#pragma unroll
+  for (int a = 0; a < 2; ++a) drop_block(d, (uint32_t)q >> 2, (uint32_t)(kb0 + 4 * s + 2 * a), w[a]);  // j = 2 s + a
+  return drop_gather_row<0>(d, w, s) | drop_gather_row<1>(d, w, s) | drop_gather_row<2>(d, w, s) |
+         drop_gather_row<3>(d, w, s) | drop_gather_row<4>(d, w, s) | drop_gather_row<5>(d, w, s) |
+         drop_gather_row<6>(d, w, s) | drop_gather_row<7>(d, w, s);
+}
+
+// dK/dV orientation (S): this lane owns key `key`, registers 4g..4g+3 of a 32-query sub-tile are the 4 queries of
+// block qb0 + 2 g (qb0 = (q0 >> 2) + h) and need byte key & 3 of all four words of that block's call.  Lane key & 3 of
+// the quad evaluates the call of g = key & 3.  Bit r is register r.
+template <int G>
+__device__ __forceinline__ uint32_t drop_gather_col(const Drop& d, const uint32_t (&w)[4], int sh) {
+  uint32_t keep = 0;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) keep |= (uint32_t)(((quad_bcast<G>(w[e]) >> sh) & 0xffu) >= d.T) << (4 * G + e);
+  return keep;
+}
+
+__device__ __forceinline__ uint32_t drop_keep_sub(const Drop& d, int qb0, int key) {
+  uint32_t w[4];
+  drop_block(d, (uint32_t)(qb0 + 2 * (key & 3)), (uint32_t)key >> 2, w);
+  const int sh = 8 * (key & 3);
+  return drop_gather_col<0>(d, w, sh) | drop_gather_col<1>(d, w, sh) | drop_gather_col<2>(d, w, sh) |
+         drop_gather_col<3>(d, w, sh);
+}
 
 template <int D>
 __device__ __forceinline__ int swz(int row) {
@@ -182,12 +297,15 @@ constexpr float RESCALE_TH = 8.f;
 // ------------------------------------------------------------------------------------------------ forward
 // NW waves x 32 queries per workgroup: one K/V tile in LDS feeds NW * 32 queries (8 waves halve the per-CU LDS-DMA
 // fill of the 4-wave form, which at the MFMA-bound rate needed ~77 GB/s per CU, above what LDS-DMA sustains).
-template <int D, int NW>
-__global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd_kernel(AttnArgs a) {
+template <int D, int NW, bool DROP>
+__global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd_kernel(KArgs<DROP> ka) {
   constexpr int QB = 32 * NW, TB = 64 * 2 * D, STAGE = 2 * TB, ND = D / 32, NS = D / 16;
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  const AttnArgs& a = attn_args(ka);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, ql = lane & 31;
   const QBlock blk = q_block<QB>(a);
+  Drop drop{};
+  if constexpr (DROP) drop = drop_load(ka, blk.b * a.H + blk.hq);
   const int q0w = blk.q0 + 32 * wave, qi = q0w + ql;
   const __bf16* Q = a.q + blk.b * a.sq.b + blk.hq * a.sq.h;
   const __bf16* K = a.k + blk.b * a.sk.b + blk.hk * a.sk.h;
@@ -220,6 +338,10 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd_kernel(Attn
     const char* Ks = smem + (j & 1) * STAGE;
     const char* Vs = Ks + TB;
     if (!(a.causal && kv0 > q0w + 31)) {  // wave-uniform: tile entirely in this wave's causal future
+      uint32_t keep = 0xffffffffu;
+      if constexpr (DROP) {
+        if (drop.T != 0) keep = drop_keep_tile(drop, qi, (kv0 >> 2) + h);  // wave-uniform
+      }
       f32x16 st[2] = {zero16(), zero16()};
 #pragma unroll
       for (int s = 0; s < NS; ++s) {
@@ -263,6 +385,13 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd_kernel(Attn
           sum += p;
         }
       l_run += sum + __shfl_xor(sum, 32);
+      if constexpr (DROP) {  // the statistics above saw the undropped p; the operand below is M o P
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+          for (int r = 0; r < 16; ++r)
+            if (!((keep >> (16 * t + r)) & 1)) st[t][r] = 0.f;
+      }
 #pragma unroll
       for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -276,7 +405,8 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd_kernel(Attn
     __syncthreads();
   }
   if (qi < a.S) {
-    const float inv = l_run > 0.f ? 1.f / l_run : 0.f;
+    float inv = l_run > 0.f ? 1.f / l_run : 0.f;
+    if constexpr (DROP) inv *= drop.c;
     store_row<D>(a.out + blk.b * a.so.b + blk.hq * a.so.h + (long long)qi * a.so.s, o, inv, h);
     if (h == 0) a.lse2[((long long)blk.b * a.H + blk.hq) * a.S + qi] = m_run + log2f(l_run);
   }
@@ -285,12 +415,15 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd_kernel(Attn
 // ------------------------------------------------------------------------------------------- backward: dQ
 // NW waves x 32 queries per workgroup: the K / V tile in LDS serves NW * 32 query rows (see the forward).  Also
 // produces delta[b][h][q] = sum_d dO . O of its rows (read from the stored bf16 O) for itself and the dK/dV kernel.
-template <int D, int NW>
-__global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_bwd_dq_kernel(AttnArgs a) {
+template <int D, int NW, bool DROP>
+__global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_bwd_dq_kernel(KArgs<DROP> ka) {
   constexpr int QB = 32 * NW, TB = 64 * 2 * D, STAGE = 2 * TB, ND = D / 32, NS = D / 16;
   extern __shared__ __attribute__((aligned(16))) char smem[];
+  const AttnArgs a = attn_args(ka);  // a copy: the plain instantiation then keeps the instruction stream it had
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, ql = lane & 31;
   const QBlock blk = q_block<QB>(a);
+  Drop drop{};
+  if constexpr (DROP) drop = drop_load(ka, blk.b * a.H + blk.hq);
   const int q0w = blk.q0 + 32 * wave, qi = q0w + ql, qc = min(qi, a.S - 1);
   const __bf16* K = a.k + blk.b * a.sk.b + blk.hk * a.sk.h;
   const __bf16* V = a.v + blk.b * a.sv.b + blk.hk * a.sv.h;
@@ -341,6 +474,10 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_bwd_dq_kernel(A
     const char* Ks = smem + (j & 1) * STAGE;
     const char* Vs = Ks + TB;
     if (!(a.causal && kv0 > q0w + 31)) {
+      uint32_t keep = 0xffffffffu;
+      if constexpr (DROP) {
+        if (drop.T != 0) keep = drop_keep_tile(drop, qi, (kv0 >> 2) + h);  // wave-uniform
+      }
       f32x16 st[2] = {zero16(), zero16()}, dp[2] = {zero16(), zero16()};
 #pragma unroll
       for (int s = 0; s < NS; ++s)
@@ -350,6 +487,12 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_bwd_dq_kernel(A
           dp[t] = mfma(row_frag<D>(Vs, 32 * t + ql, 2 * s + h), gf[s], dp[t]);
         }
       const bool mask = (a.causal && kv0 + 63 > q0w) || kv0 + 64 > a.Skv || qi >= a.S;
+      if constexpr (DROP) {  // dP^T = c M o (V dO^T), before the subtraction of delta
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) dp[t][r] = (keep >> (16 * t + r)) & 1 ? dp[t][r] * drop.c : 0.f;
+      }
 #pragma unroll
       for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -528,10 +671,11 @@ __global__ __launch_bounds__(NT, 1) void attn_bwd_dkdv_kernel(AttnArgs a, float*
 // come straight from global memory into registers (they are fixed for the whole sweep), so LDS holds only the
 // double-buffered { Q tile [64][D] | dO tile [64][D] | lse2[64] | delta[64] } stages; the bf16 dK / dV rows (no GQA)
 // are staged through that region one tensor at a time.
-template <int D>
-__global__ __launch_bounds__(512, 1) void attn_bwd_dkdv8_kernel(AttnArgs a, float* __restrict__ ws) {
+template <int D, bool DROP>
+__global__ __launch_bounds__(512, 1) void attn_bwd_dkdv8_kernel(KArgs<DROP> ka, float* __restrict__ ws) {
   constexpr int NW = 8, KBLK = 32 * NW, QTB = 64 * 2 * D, QSTAGE = 2 * QTB + 512, ND = D / 32, NS = D / 16;
   extern __shared__ __attribute__((aligned(16))) char lds[];
+  const AttnArgs& a = attn_args(ka);
   char* Vimg = lds;                                    // [256][D] V rows of this key block
   char* smem = lds + KBLK * 2 * D;                     // 2 Q / dO stages
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5, kl = lane & 31;
@@ -542,6 +686,8 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_dkdv8_kernel(AttnArgs a, floa
   const int b = bh / a.H, hq = bh % a.H, G = a.H / a.Hkv, hk = hq / G;
   const int k0 = kb * KBLK, kw0 = k0 + 32 * wave;
   (void)nkb;
+  Drop drop{};
+  if constexpr (DROP) drop = drop_load(ka, bh);
   const __bf16* Qh = a.q + b * a.sq.b + hq * a.sq.h;
   const __bf16* Gh = a.dout + b * a.sdo.b + hq * a.sdo.h;
   const long long srow0 = ((long long)b * a.H + hq) * a.S;
@@ -588,6 +734,10 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_dkdv8_kernel(AttnArgs a, floa
     for (int sub = 0; sub < 2; ++sub) {
       const int q0 = (qt0 + it) * 64 + 32 * sub;
       if (a.causal && q0 + 31 < kw0) continue;  // wave-uniform: every query precedes this wave's keys
+      uint32_t keep = 0xffffu;
+      if constexpr (DROP) {
+        if (drop.T != 0) keep = drop_keep_sub(drop, (q0 >> 2) + h, key);  // wave-uniform
+      }
       f32x16 s_acc = zero16(), dp = zero16();
 #pragma unroll
       for (int s = 0; s < NS; ++s) {
@@ -608,8 +758,14 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_dkdv8_kernel(AttnArgs a, floa
             const int q = q0 + 8 * g + 4 * h + e;
             if ((a.causal && key > q) || q >= a.S || key >= a.Skv) p = 0.f;
           }
-          s_acc[r] = p;
-          dp[r] = p * (dp[r] - dv4[e]);
+          if constexpr (DROP) {
+            const bool kept = (keep >> r) & 1;
+            s_acc[r] = kept ? p : 0.f;                  // the dV operand M o P (c on the finished rows)
+            dp[r] = p * ((kept ? dp[r] * drop.c : 0.f) - dv4[e]);
+          } else {
+            s_acc[r] = p;
+            dp[r] = p * (dp[r] - dv4[e]);
+          }
         }
       }
 #pragma unroll
@@ -624,6 +780,12 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_dkdv8_kernel(AttnArgs a, floa
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
+  }
+  if constexpr (DROP) {  // dV = (c M o P)^T dO: c on the finished rows
+#pragma unroll
+    for (int dt = 0; dt < ND; ++dt)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) dv[dt][r] *= drop.c;
   }
   if (G > 1) {
     // fp32 partials of this query head: ws[{dk, dv}][b][hq][key][d]; rows = keys (registers), column = d (lane)
@@ -714,13 +876,14 @@ bool args_ok(const AttnArgs& a, int D) {
 // forward waves per workgroup (A/B knob plx_attn_set_fwd_waves: 4 or 8)
 int g_fwd_waves = 8;
 
-template <int D, int NW>
-int launch_fwd(const AttnArgs& a, hipStream_t stream) {
+template <int D, int NW, bool DROP = false>
+int launch_fwd(const KArgs<DROP>& ka, hipStream_t stream) {
   constexpr int LDS = 4 * 64 * 2 * D;  // 2 stages x {K, V} x 64 rows
-  static int once = prepare(attn_fwd_kernel<D, NW>, LDS);
+  static int once = prepare(attn_fwd_kernel<D, NW, DROP>, LDS);
   if (once) return once;
+  const AttnArgs& a = attn_args(ka);
   const int grid = ((a.S + 32 * NW - 1) / (32 * NW)) * a.H * a.B;
-  hipLaunchKernelGGL((attn_fwd_kernel<D, NW>), dim3(grid), dim3(64 * NW), LDS, stream, a);
+  hipLaunchKernelGGL((attn_fwd_kernel<D, NW, DROP>), dim3(grid), dim3(64 * NW), LDS, stream, ka);
   return (int)hipGetLastError();
 }
 
@@ -743,23 +906,24 @@ PLX_API long long plx_attn_bwd_workspace(int B, int H, int Hkv, int Skv, int D) 
 // dQ / dK-dV waves per workgroup (A/B knobs plx_attn_set_dq_waves / plx_attn_set_dkdv_waves: 4 or 8)
 int g_dq_waves = 8, g_dkdv_waves = 8;
 
-template <int D>
-int launch_bwd(const AttnArgs& a, float* ws, hipStream_t stream) {
+template <int D, bool DROP = false>
+int launch_bwd(const KArgs<DROP>& ka, float* ws, hipStream_t stream) {
   constexpr int QLDS = 4 * 64 * 2 * D, KLDS = 2 * 128 * 2 * D + 2 * (2 * 64 * 2 * D + 512);
   constexpr int KLDS8 = 256 * 2 * D + 2 * (2 * 64 * 2 * D + 512);
   static_assert(KLDS8 - 256 * 2 * D >= 256 * D * 2, "the dK / dV output staging must fit the stage region");
-  static int once = prepare(attn_bwd_dq_kernel<D, 4>, QLDS) | prepare(attn_bwd_dq_kernel<D, 8>, QLDS) |
-                    prepare(attn_bwd_dkdv_kernel<D>, KLDS) | prepare(attn_bwd_dkdv8_kernel<D>, KLDS8);
+  static int once = prepare(attn_bwd_dq_kernel<D, 4, DROP>, QLDS) | prepare(attn_bwd_dq_kernel<D, 8, DROP>, QLDS) |
+                    (DROP ? 0 : prepare(attn_bwd_dkdv_kernel<D>, KLDS)) | prepare(attn_bwd_dkdv8_kernel<D, DROP>, KLDS8);
   if (once) return once;
+  const AttnArgs& a = attn_args(ka);
   const int qb = 32 * g_dq_waves;
   const int qgrid = ((a.S + qb - 1) / qb) * a.H * a.B;
   const int kgrid = ((a.Skv + 127) / 128) * a.H * a.B;
   // the dQ kernel goes first: it writes delta, which the dK/dV kernel reads
-  if (g_dq_waves == 4) hipLaunchKernelGGL((attn_bwd_dq_kernel<D, 4>), dim3(qgrid), dim3(256), QLDS, stream, a);
-  else hipLaunchKernelGGL((attn_bwd_dq_kernel<D, 8>), dim3(qgrid), dim3(512), QLDS, stream, a);
-  if (g_dkdv_waves == 8)
-    hipLaunchKernelGGL(attn_bwd_dkdv8_kernel<D>, dim3(((a.Skv + 255) / 256) * a.H * a.B), dim3(512), KLDS8, stream, a,
-                       ws);
+  if (g_dq_waves == 4) hipLaunchKernelGGL((attn_bwd_dq_kernel<D, 4, DROP>), dim3(qgrid), dim3(256), QLDS, stream, ka);
+  else hipLaunchKernelGGL((attn_bwd_dq_kernel<D, 8, DROP>), dim3(qgrid), dim3(512), QLDS, stream, ka);
+  if (DROP || g_dkdv_waves == 8)  // the 4-wave dK/dV kernel has no dropout: a dropout launch always takes this one
+    hipLaunchKernelGGL((attn_bwd_dkdv8_kernel<D, DROP>), dim3(((a.Skv + 255) / 256) * a.H * a.B), dim3(512), KLDS8,
+                       stream, ka, ws);
   else hipLaunchKernelGGL(attn_bwd_dkdv_kernel<D>, dim3(kgrid), dim3(NT), KLDS, stream, a, ws);
   if (a.H != a.Hkv) {
     const long long n8 = (long long)a.B * a.Hkv * a.Skv * (D / 8);
@@ -772,14 +936,45 @@ int launch_bwd(const AttnArgs& a, float* ws, hipStream_t stream) {
 PLX_API void plx_attn_set_dq_waves(int nw) { g_dq_waves = nw == 4 ? 4 : 8; }
 PLX_API void plx_attn_set_dkdv_waves(int nw) { g_dkdv_waves = nw == 4 ? 4 : 8; }
 
-PLX_API int plx_attn_bwd(const AttnArgs* args, int D, float* ws, hipStream_t stream) {
-  const AttnArgs& a = *args;
+static int bwd_args_check(const AttnArgs& a, int D, const float* ws) {
   if (!args_ok(a, D)) return 1;
   const long long strides[] = {a.so.s, a.sdo.s, a.sdq.s, a.sdk.s, a.sdv.s, a.so.h, a.sdo.h, a.sdq.h, a.sdk.h, a.sdv.h};
   for (long long s : strides)
     if (s % 8) return 1;
   if (a.H != a.Hkv && ws == nullptr) return 2;
+  return 0;
+}
+
+PLX_API int plx_attn_bwd(const AttnArgs* args, int D, float* ws, hipStream_t stream) {
+  const AttnArgs& a = *args;
+  if (const int rc = bwd_args_check(a, D, ws)) return rc;
   return D == 128 ? launch_bwd<128>(a, ws, stream) : launch_bwd<64>(a, ws, stream);
+}
+
+// Attention dropout (the contract at the top of this file): the plain entry points' checks, plus hp / step present and
+// the limits of the counter word.  A refused call launches nothing.
+static bool drop_ok(const AttnArgs& a, const uint32_t* hp, const int32_t* step, int layer) {
+  if (hp == nullptr || step == nullptr || layer < 0 || layer >= 32768) return false;
+  return (long long)a.B * a.H < 65536;  // b * H + h fits the counter word's low 16 bits
+}
+
+PLX_API int plx_attn_drop_fwd(const AttnArgs* args, const uint32_t* hp, const int32_t* step, int layer, int D,
+                              hipStream_t stream) {
+  const AttnArgs& a = *args;
+  if (!args_ok(a, D) || !drop_ok(a, hp, step, layer)) return 1;
+  if (a.so.s % 4 || a.so.h % 4 || a.so.b % 4) return 1;
+  const AttnDropArgs ka{a, hp, step, (uint32_t)layer};
+  if (D == 128) return g_fwd_waves == 4 ? launch_fwd<128, 4, true>(ka, stream) : launch_fwd<128, 8, true>(ka, stream);
+  return g_fwd_waves == 4 ? launch_fwd<64, 4, true>(ka, stream) : launch_fwd<64, 8, true>(ka, stream);
+}
+
+PLX_API int plx_attn_drop_bwd(const AttnArgs* args, const uint32_t* hp, const int32_t* step, int layer, int D,
+                              float* ws, hipStream_t stream) {
+  const AttnArgs& a = *args;
+  if (const int rc = bwd_args_check(a, D, ws)) return rc;
+  if (!drop_ok(a, hp, step, layer)) return 1;
+  const AttnDropArgs ka{a, hp, step, (uint32_t)layer};
+  return D == 128 ? launch_bwd<128, true>(ka, ws, stream) : launch_bwd<64, true>(ka, ws, stream);
 }
 
 PLX_API int plx_attn_args_size() { return (int)sizeof(AttnArgs); }

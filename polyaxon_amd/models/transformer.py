@@ -119,6 +119,7 @@ class Attention(nn.Module):
         hd = cfg.head_dim
         self.qkv = nn.Linear(cfg.d_model, (cfg.n_heads + 2 * cfg.kv_heads) * hd, bias=cfg.bias)
         self.proj = nn.Linear(cfg.n_heads * hd, cfg.d_model, bias=cfg.bias)
+        self._drop = None  # (AttnDropoutState, layer index): Transformer.set_attn_dropout
 
     def forward(self, x, rope=None):
         B, S, _ = x.shape
@@ -138,7 +139,12 @@ class Attention(nn.Module):
                 q, k = apply_rope(q, *cs), apply_rope(k, *cs)
         # hand-written CDNA4 flash attention (ops/attention.py, csrc/attn_kernels.hip): GQA straight into the
         # kernel (no repeat_interleave of K/V), output written in [B, S, H, D] so the projection reads it as is
-        y = flash_attention(q, k, v, causal=True)
+        if self._drop is not None and self.training:
+            # dropout on the probabilities inside the kernels (ops/attn_dropout.py); an activation-checkpoint
+            # recomputation runs at the same step, so it draws the same mask
+            y = flash_attention(q, k, v, causal=True, drop=self._drop)
+        else:
+            y = flash_attention(q, k, v, causal=True)
         return lm_ops.linear(y.reshape(B, S, cfg.n_heads * hd), self.proj.weight, self.proj.bias, side=True)
 
 
@@ -206,6 +212,13 @@ class Transformer(nn.Module):
         self._drop = state
         for l, blk in enumerate(self.blocks):
             blk._drop = None if state is None else (state, l)
+
+    def set_attn_dropout(self, state) -> None:
+        """Attention dropout (GPT-2's ``attn_pdrop``) with its rate in device memory (ops/attn_dropout.py
+        AttnDropoutState): the attention of block l draws the masks of layer l.  None, or ``eval()``: the plain
+        attention call."""
+        for l, blk in enumerate(self.blocks):
+            blk.attn._drop = None if state is None else (state, l)
 
     def init_spec(self):
         """(param, kind, scale) for the fused in-place re-initialiser (GPT-2 / Llama conventions)."""

@@ -335,6 +335,8 @@ SIGNATURES: Dict[str, Dict[str, list]] = {
     "plx_attn": {
         "plx_attn_fwd": [_P, _I, _P],
         "plx_attn_bwd": [_P, _I, _P, _P],
+        "plx_attn_drop_fwd": [_P, _P, _P, _I, _I, _P],  # (AttnArgs*, hp, step, layer, D, stream)
+        "plx_attn_drop_bwd": [_P, _P, _P, _I, _I, _P, _P],  # (AttnArgs*, hp, step, layer, D, ws, stream)
         "plx_attn_bwd_workspace": [_I, _I, _I, _I, _I],
         "plx_attn_args_size": [],
         "plx_attn_set_fwd_waves": [_I],

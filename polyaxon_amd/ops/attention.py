@@ -10,6 +10,10 @@ no atomics).
 
 CPU tensors, fp32 and other head dims use the plain fp32 math definition (``_reference``); bf16 with head_dim
 64 / 128 on a GPU -- every training config -- always runs the HIP kernels.
+
+``drop=(AttnDropoutState, layer)`` is dropout on the softmax probabilities (ops/attn_dropout.py): the kernels'
+``plx_attn_drop_*`` entry points read the rate and the step counter from device memory and regenerate the mask in
+the forward and in both backward kernels; nothing is stored.  ``drop=None`` is exactly the plain path.
 """
 from __future__ import annotations
 
@@ -70,9 +74,23 @@ def _args(q, k, v, causal: bool, scale: float) -> _AttnArgs:
     return a
 
 
-def _reference(q, k, v, causal, scale):
+def _reference_mask(drop, B, H, S, Skv, device):
+    """[B, H, S, Skv] fp32: c where the probability is kept, 0 where it is dropped -- the host twin's mask at the
+    step the device counter holds (one ``.item()``: the fallback only)."""
+    import numpy as np
+
+    from polyaxon_amd.ops import attn_dropout
+
+    state, layer = drop
+    step, T = state.step(), state.T
+    m = np.stack([attn_dropout.mask_reference(state.key, step, layer, bh, S, Skv, T) for bh in range(B * H)])
+    return torch.from_numpy(m.reshape(B, H, S, Skv)).to(device=device, dtype=torch.float32) * state.c
+
+
+def _reference(q, k, v, causal, scale, drop=None):
     """Plain fp32 math (matmul + softmax): the CPU path and the path for shapes / dtypes the HIP kernel does not
-    take (fp32 reference models, head_dim other than 64 / 128).  No SDPA, so no library attention kernel."""
+    take (fp32 reference models, head_dim other than 64 / 128).  No SDPA, so no library attention kernel.  ``drop``:
+    the softmax is multiplied by the twin's scaled mask (ops/attn_dropout.py)."""
     rep = q.shape[1] // k.shape[1]
     kk = k.repeat_interleave(rep, 1) if rep > 1 else k
     vv = v.repeat_interleave(rep, 1) if rep > 1 else v
@@ -80,7 +98,10 @@ def _reference(q, k, v, causal, scale):
     if causal:
         S, Sk = q.shape[2], k.shape[2]
         s = s.masked_fill(torch.ones(S, Sk, dtype=torch.bool, device=q.device).triu(1), float("-inf"))
-    o = torch.matmul(s.softmax(-1), vv.float()).to(q.dtype)
+    p = s.softmax(-1)
+    if drop is not None:
+        p = p * _reference_mask(drop, q.shape[0], q.shape[1], q.shape[2], k.shape[2], q.device)
+    o = torch.matmul(p, vv.float()).to(q.dtype)
     return o.transpose(1, 2)
 
 
@@ -100,7 +121,7 @@ def _lib():
 
 class _FlashAttention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, causal: bool, scale: float):
+    def forward(ctx, q, k, v, causal: bool, scale: float, drop=None):
         lib = _lib()
         q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
         B, H, S, D = q.shape
@@ -108,10 +129,16 @@ class _FlashAttention(torch.autograd.Function):
         lse2 = torch.empty(B, H, S, dtype=torch.float32, device=q.device)
         a = _args(q, k, v, causal, scale)
         a.out, a.so, a.lse2 = out.data_ptr(), _bhs(out, "bshd"), lse2.data_ptr()
-        rc = lib.plx_attn_fwd(ctypes.byref(a), D, torch.cuda.current_stream(q.device).cuda_stream)
-        _native.check(rc, "plx_attn_fwd")
+        stream = torch.cuda.current_stream(q.device).cuda_stream
+        if drop is None:
+            _native.check(lib.plx_attn_fwd(ctypes.byref(a), D, stream), "plx_attn_fwd")
+        else:
+            state, layer = drop
+            rc = lib.plx_attn_drop_fwd(ctypes.byref(a), state.hp.data_ptr(), state.step_counter.data_ptr(), layer, D,
+                                       stream)
+            _native.check(rc, "plx_attn_drop_fwd")
         ctx.save_for_backward(q, k, v, out, lse2)
-        ctx.causal, ctx.scale = causal, scale
+        ctx.causal, ctx.scale, ctx.drop = causal, scale, drop
         return out
 
     @staticmethod
@@ -131,21 +158,29 @@ class _FlashAttention(torch.autograd.Function):
         a.lse2, a.delta = lse2.data_ptr(), delta.data_ptr()
         nbytes = int(lib.plx_attn_bwd_workspace(B, H, k.shape[1], k.shape[2], D))
         ws = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=q.device) if nbytes else None
-        rc = lib.plx_attn_bwd(ctypes.byref(a), D, ws.data_ptr() if ws is not None else None,
-                              torch.cuda.current_stream(q.device).cuda_stream)
-        _native.check(rc, "plx_attn_bwd")
-        return dq, dk, dv, None, None
+        wsp = ws.data_ptr() if ws is not None else None
+        stream = torch.cuda.current_stream(q.device).cuda_stream
+        if ctx.drop is None:
+            _native.check(lib.plx_attn_bwd(ctypes.byref(a), D, wsp, stream), "plx_attn_bwd")
+        else:  # the same step as the forward: the three kernels redraw its mask
+            state, layer = ctx.drop
+            rc = lib.plx_attn_drop_bwd(ctypes.byref(a), state.hp.data_ptr(), state.step_counter.data_ptr(), layer, D,
+                                       wsp, stream)
+            _native.check(rc, "plx_attn_drop_bwd")
+        return dq, dk, dv, None, None, None
 
 
 def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = True,
-                    scale: Optional[float] = None) -> torch.Tensor:
+                    scale: Optional[float] = None, drop=None) -> torch.Tensor:
     """softmax(q k^T * scale [+ causal mask]) v with GQA (H % Hkv == 0).  q: [B,H,S,D], k/v: [B,Hkv,Skv,D].
-    Returns [B, S, H, D]."""
+    Returns [B, S, H, D].  ``drop=(AttnDropoutState, layer)``: dropout on the probabilities (module docstring)."""
     if q.dim() != 4 or k.dim() != 4 or v.shape != k.shape or q.shape[-1] != k.shape[-1]:
         raise ValueError("expected q [B,H,S,D] and k/v [B,Hkv,Skv,D]")
     if q.shape[1] % k.shape[1]:
         raise ValueError("query heads must be a multiple of key/value heads")
     scale = 1.0 / math.sqrt(q.shape[-1]) if scale is None else float(scale)
     if not q.is_cuda or q.dtype != torch.bfloat16 or q.shape[-1] not in (64, 128):
-        return _reference(q, k, v, causal, scale)
-    return _FlashAttention.apply(q, k, v, causal, scale)
+        return _reference(q, k, v, causal, scale, drop)
+    if drop is None:
+        return _FlashAttention.apply(q, k, v, causal, scale)
+    return _FlashAttention.apply(q, k, v, causal, scale, drop)

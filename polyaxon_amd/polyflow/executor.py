@@ -52,7 +52,8 @@ class ResidentTrialExecutor:
                  amp_dtype: Optional[torch.dtype] = torch.bfloat16, channels_last: bool = True,
                  ring_size: int = 4096, init_spec: Optional[Callable] = None,
                  lp_dtype: Optional[torch.dtype] = None, clip_grad: bool = False, lr_schedule=False,
-                 loss_hparams: bool = False, dropout: bool = False, dropout_seed: int = 0):
+                 loss_hparams: bool = False, dropout: bool = False, dropout_seed: int = 0,
+                 attn_dropout: bool = False):
         """``lp_dtype`` (the language models, GPU): the model computes from bf16 weights with bf16 gradients and the
         optimizer keeps the fp32 master (ops/flat.py lp mode); every re-init / restore refreshes the bf16 copy.
         ``clip_grad``: global-norm gradient clipping (ops/optim.py) with ``max_grad_norm`` as one more device
@@ -70,7 +71,11 @@ class ResidentTrialExecutor:
         ``set_dropout`` gets a state built on this executor's step counter, so the captured step draws fresh masks
         every replay and its backward regenerates them; the rate starts at 0 -- bitwise the plain step -- until a
         trial sets one.  ``dropout_seed`` keys the masks (not the trial's init seed: every trial sees the same
-        masks, and a restored snapshot continues the stream from its step counter alone)."""
+        masks, and a restored snapshot continues the stream from its step counter alone).
+        ``attn_dropout``: dropout on the attention probabilities, its rate ``attn_dropout`` one more device
+        hyper-parameter (ops/attn_dropout.py): the model's ``set_attn_dropout`` gets a state built on this executor's
+        step counter and keyed by ``dropout_seed``; the flash-attention kernels redraw the mask in the forward and the
+        backward.  Independent of ``dropout``; 0 -- bitwise the plain step -- until a trial sets a rate."""
         self.device = torch.device(device)
         self.is_cuda = self.device.type == "cuda"
         if channels_last:
@@ -99,6 +104,15 @@ class ResidentTrialExecutor:
 
             self.dropout = DropoutState(self.device, self.step, seed=dropout_seed)
             model.set_dropout(self.dropout)
+        self.attn_dropout = None
+        if attn_dropout:
+            if not hasattr(model, "set_attn_dropout"):
+                raise ValueError(f"attn_dropout=True needs a model with set_attn_dropout(); {type(model).__name__} "
+                                 "has no attention")
+            from polyaxon_amd.ops.attn_dropout import AttnDropoutState
+
+            self.attn_dropout = AttnDropoutState(self.device, self.step, seed=dropout_seed)
+            model.set_attn_dropout(self.attn_dropout)
         # default: cross entropy of the fp32-cast logits; on the GPU in one fused HIP kernel each way (ops/lm.py
         # class_xent: no fp32 logits copy, log-softmax or NLL kernels between the head GEMM and its backward, where the
         # host launching them was the bottleneck of the forward -> backward hand-off; +0.1-0.2 %, r5_class_xent_ab.jsonl)
@@ -170,6 +184,10 @@ class ResidentTrialExecutor:
             import torch.distributed as dist
 
             self.dropout.set_rank(dist.get_rank(process_group))
+        if self.attn_dropout is not None:
+            import torch.distributed as dist
+
+            self.attn_dropout.set_rank(dist.get_rank(process_group))
         self.use_graph = False
         self._prefetch = False
 
@@ -349,6 +367,8 @@ class ResidentTrialExecutor:
                 self.loss_hp.set(**own)
         if self.dropout is not None and "dropout" in hp:
             self.dropout.set(dropout=hp["dropout"])
+        if self.attn_dropout is not None and "attn_dropout" in hp:
+            self.attn_dropout.set(attn_dropout=hp["attn_dropout"])
         self.opt.set_hparams(**{k: v for k, v in hp.items() if k in self.opt.HP})
 
     def grad_norm(self) -> torch.Tensor:

@@ -29,6 +29,11 @@ with different smoothing stay comparable.
 device data and no mask is stored: the step's kernels draw it from the device step counter, so one captured step
 serves every rate and draws fresh masks every replay.  ``dropout_seed`` keys the masks for the whole program, so
 trials differ by their weights and rates, not by their masks.  The other programs have no dropout sites and reject it.
+
+``gpt2`` and ``gpt2_tiny`` also take ``params: {attn_dropout: true}``: dropout on the attention probabilities
+(ops/attn_dropout.py, drawn inside the flash-attention kernels) with the rate ``attn_dropout`` as a per-trial
+hyper-parameter, 0 until a trial sets it.  It is independent of ``dropout`` -- either or both may be on -- and shares
+``dropout_seed``.  The other programs reject it.
 """
 from __future__ import annotations
 
@@ -77,6 +82,10 @@ class TrialProgram:
                 from polyaxon_amd.ops import dropout
 
                 ex.set_hparams(**dropout.DEFAULTS)
+            if self.info.get("attn_dropout"):
+                from polyaxon_amd.ops import attn_dropout
+
+                ex.set_hparams(**attn_dropout.DEFAULTS)
         if ex.is_cuda:
             torch.cuda.synchronize(ex.device)
 
@@ -114,9 +123,27 @@ def _dropout(params: Dict[str, Any]) -> bool:
     return bool(params.get("dropout", False))
 
 
+def _attn_dropout(params: Dict[str, Any]) -> bool:
+    return bool(params.get("attn_dropout", False))
+
+
 def _no_dropout(name: str, params: Dict[str, Any]) -> None:
     if _dropout(params) or "dropout_seed" in params:
         raise ValueError(f"program {name} has no dropout sites: `dropout` is a param of gpt2 / gpt2_tiny only")
+    if _attn_dropout(params):
+        raise ValueError(f"program {name} has no attention: `attn_dropout` is a param of gpt2 / gpt2_tiny only")
+
+
+def _with_attn_dropout(prog: TrialProgram, on: bool) -> TrialProgram:
+    """``attn_dropout`` programs understand the ``attn_dropout`` rate and warm up at 0.1, so the warm steps draw
+    masks."""
+    if on:
+        from polyaxon_amd.ops import attn_dropout
+
+        prog.hp_keys = prog.hp_keys + attn_dropout.KEYS
+        prog.info["warm_hparams"] = {**prog.info.get("warm_hparams", {}), "attn_dropout": 0.1}
+        prog.info["attn_dropout"] = True
+    return prog
 
 
 def _with_dropout(prog: TrialProgram, on: bool) -> TrialProgram:
@@ -226,8 +253,9 @@ def _gpt2(params: Dict[str, Any], device, tiny: bool) -> TrialProgram:
 
     dev = torch.device(device)
     if tiny:
-        cfg = gpt2_125m(vocab_size=int(params.get("vocab", 256)), n_layers=2, d_model=64, n_heads=2, d_ff=256,
-                        max_seq_len=int(params.get("seq", 32)))
+        # heads: 1 gives head_dim 64, the smallest the flash-attention kernels take (2: the fp32 math fallback)
+        cfg = gpt2_125m(vocab_size=int(params.get("vocab", 256)), n_layers=2, d_model=64,
+                        n_heads=int(params.get("heads", 2)), d_ff=256, max_seq_len=int(params.get("seq", 32)))
     else:
         cfg = gpt2_125m(vocab_size=int(params.get("vocab", 50257)))
     batch = int(params.get("batch", 2 if tiny else 16))
@@ -252,8 +280,8 @@ def _gpt2(params: Dict[str, Any], device, tiny: bool) -> TrialProgram:
                                use_graph=bool(params.get("graph", False)), channels_last=False,
                                lp_dtype=torch.bfloat16, clip_grad=clip, lr_schedule=_lr_schedule(params),
                                loss_hparams=loss_hp, dropout=_dropout(params),
-                               dropout_seed=int(params.get("dropout_seed", 0)))
-    return _with_dropout(_with_loss_hp(_with_schedule(_with_clip(TrialProgram(
+                               dropout_seed=int(params.get("dropout_seed", 0)), attn_dropout=_attn_dropout(params))
+    return _with_attn_dropout(_with_dropout(_with_loss_hp(_with_schedule(_with_clip(TrialProgram(
         ex, unit_steps=int(params.get("unit_steps", 4 if tiny else 10)),
         window=int(params.get("window", 4)),
         hp_keys=("lr", "beta1", "beta2", "eps", "weight_decay"),
@@ -263,7 +291,7 @@ def _gpt2(params: Dict[str, Any], device, tiny: bool) -> TrialProgram:
                                "weight_decay": 0.1},
               "tokens_per_step": batch * seq, "floor_loss": data.floor_loss,
               "unigram_loss": data.unigram_loss, "chance_loss": data.chance_loss,
-              "active_vocab": data.active_vocab}), clip), params), loss_hp), _dropout(params))
+              "active_vocab": data.active_vocab}), clip), params), loss_hp), _dropout(params)), _attn_dropout(params))
 
 
 PROGRAMS: Dict[str, Callable[[Dict[str, Any], Any], TrialProgram]] = {

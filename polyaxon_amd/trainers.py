@@ -247,6 +247,9 @@ def train_lm(argv=None) -> float:
     ap.add_argument("--dropout", type=float, default=0.0,
                     help="residual and embedding dropout rate (ops/dropout.py: device data, masks regenerated in the "
                          "backward from the step counter); 0: no dropout state, the plain launches")
+    ap.add_argument("--attn-dropout", "--attn_dropout", dest="attn_dropout", type=float, default=0.0,
+                    help="dropout rate on the attention probabilities (ops/attn_dropout.py: device data, masks redrawn "
+                         "inside the flash-attention kernels from the step counter); 0: no state, the plain kernels")
     _schedule_args(ap, warmup=False)  # --warmup_steps above: host-side without a schedule, the schedule's with one
     _loss_args(ap)
     args = _parse(ap, argv)
@@ -312,6 +315,12 @@ def train_lm(argv=None) -> float:
         drop = DropoutState(dev, step, rank=info["rank"])
         drop.set(dropout=args.dropout)
         model.set_dropout(drop)
+    if args.attn_dropout != 0:  # device data of the attention kernels; 0: not built at all
+        from polyaxon_amd.ops.attn_dropout import AttnDropoutState
+
+        attn_drop = AttnDropoutState(dev, step, rank=info["rank"])  # `step`: the same rule as above
+        attn_drop.set(attn_dropout=args.attn_dropout)
+        model.set_attn_dropout(attn_drop)
     metrics = MetricReducer(dev, force_comm=force)  # cross-rank mean of the logged loss (RCCL communicator, GPU)
     g = torch.Generator(device=dev).manual_seed(args.seed + 1000 * info["rank"])
 
