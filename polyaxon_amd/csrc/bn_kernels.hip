@@ -229,44 +229,103 @@ struct BwdFin {
   int accumulate;
 };
 
-template <int NT, bool ATOMIC = false>
-__device__ __forceinline__ void fwd_finalize(const float* psum, const float* psq, int nblk, const FwdFin& f) {
-  double S, Q;  // level-2 partials per channel, summed in fp64
-  if (!fin_sum2<NT, ATOMIC>(psum, psq, nblk, f.C, S, Q)) return;
-  const int c = blockIdx.x * 64 + (threadIdx.x & 63);
+// The per-channel values a finalize reads besides the sums.  None depends on the sums, so the one-launch kernels load
+// them BEFORE the partial rows: behind the sums each was one more dependent round trip on the critical path of every
+// BatchNorm, dbeta / dgamma's two behind a branch on `accumulate`.  Every load is unconditional: dgamma / dbeta are
+// read whatever `accumulate` says and the value is dropped when it is not wanted.
+struct FwdPar {
+  float gamma, beta, rmean, rvar, x0;
+};
+
+struct BwdPar {
+  float gamma, mean, invstd, dgamma, dbeta;
+};
+
+// A raw buffer descriptor over `bytes` bytes at p (wave-uniform inputs only): a load through it at an offset >= bytes
+// reads nothing and returns 0.  That is how these kernels drop a value without a select on it: hipcc turns
+// `ok ? p[i] : 0.f` into a branch around the load with an `s_waitcnt vmcnt(0)` behind it, one dependent round trip
+// per row (cdna_hip_programming.md, buffer addressing)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc(const void* p, int bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
+}
+
+// p[c] for the lanes that are `on`, +0 (and no access) for the others and for a null p: nothing is predicated, so
+// every wave issues these loads and moves on
+__device__ __forceinline__ float par_load(const float* p, int C, int c, bool on) {
+  const int bytes = p != nullptr ? C * (int)sizeof(float) : 0;
+  return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(buf_rsrc(p, bytes), on ? c * (int)sizeof(float) : bytes, 0, 0));
+}
+
+// on: this thread finalizes channel c if any thread of its block does
+__device__ __forceinline__ FwdPar fwd_params(const FwdFin& f, int c, bool on) {
+  FwdPar p;
+  p.gamma = par_load(f.gamma, f.C, c, on);
+  p.beta = par_load(f.beta, f.C, c, on);
+  p.rmean = par_load(f.running_mean, f.C, c, on);
+  p.rvar = par_load(f.running_mean != nullptr ? f.running_var : nullptr, f.C, c, on);
+  const int xbytes = f.x_row0 != nullptr ? 2 * f.C : 0;  // null x_row0: 0 = +0.f
+  p.x0 = bf2f((uint16_t)__builtin_amdgcn_raw_buffer_load_b16(buf_rsrc(f.x_row0, xbytes), on ? 2 * c : xbytes, 0, 0));
+  return p;
+}
+
+__device__ __forceinline__ BwdPar bwd_params(const BwdFin& f, int c, bool on) {
+  BwdPar p;
+  p.gamma = par_load(f.gamma, f.C, c, on);
+  p.mean = par_load(f.mean, f.C, c, on);
+  p.invstd = par_load(f.invstd, f.C, c, on);
+  p.dgamma = par_load(f.dgamma, f.C, c, on);
+  p.dbeta = par_load(f.dbeta, f.C, c, on);
+  return p;
+}
+
+// Everything after the sums: S, Q are channel c's fp64 totals of the shifted sum and sum of squares
+__device__ __forceinline__ void fwd_finish(const FwdFin& f, int c, double S, double Q, const FwdPar& p) {
   const double m = S / (double)f.M;
   double var = Q / (double)f.M - m * m;
   if (var < 0.0) var = 0.0;
-  const float mean = (f.x_row0 != nullptr ? bf2f(f.x_row0[c]) : 0.f) + (float)m;
+  const float mean = p.x0 + (float)m;
   const float invstd = rsqrtf((float)var + f.eps);
-  const float g = f.gamma[c];
+  const float g = p.gamma;
   f.save_mean[c] = mean;
   f.save_invstd[c] = invstd;
   f.scale[c] = g * invstd;
-  f.bias[c] = f.beta[c] - mean * g * invstd;
+  f.bias[c] = p.beta - mean * g * invstd;
   if (f.running_mean != nullptr) {
     const float unbiased = f.M > 1 ? (float)(var * (double)f.M / (double)(f.M - 1)) : (float)var;
-    f.running_mean[c] = (1.f - f.momentum) * f.running_mean[c] + f.momentum * mean;
-    f.running_var[c] = (1.f - f.momentum) * f.running_var[c] + f.momentum * unbiased;
+    f.running_mean[c] = (1.f - f.momentum) * p.rmean + f.momentum * mean;
+    f.running_var[c] = (1.f - f.momentum) * p.rvar + f.momentum * unbiased;
   }
 }
 
-template <int NT, bool ATOMIC = false>
-__device__ __forceinline__ void bwd_finalize(const float* pdz, const float* pdzx, int nblk, const BwdFin& f) {
-  double A, B;
-  if (!fin_sum2<NT, ATOMIC>(pdz, pdzx, nblk, f.C, A, B)) return;
+// A, B: channel c's fp64 totals of dz and dz * xhat
+__device__ __forceinline__ void bwd_finish(const BwdFin& f, int c, double A, double B, const BwdPar& p) {
   const int C = f.C;
-  const int c = blockIdx.x * 64 + (threadIdx.x & 63);
   const float db = (float)A, dg = (float)B;
   // accumulate: dgamma / dbeta are the parameters' own (flat) gradient slots, summed into like autograd would
-  f.dbeta[c] = f.accumulate ? f.dbeta[c] + db : db;
-  f.dgamma[c] = f.accumulate ? f.dgamma[c] + dg : dg;
-  const float is = f.invstd[c], k1 = f.gamma[c] * is;
+  f.dbeta[c] = f.accumulate ? p.dbeta + db : db;
+  f.dgamma[c] = f.accumulate ? p.dgamma + dg : dg;
+  const float is = p.invstd, k1 = p.gamma * is;
   const float k2 = db / (float)f.M, k3 = dg / (float)f.M;
   // dx = k1 * (dz - k2 - xhat*k3),  xhat = (x - mean) * is   =>  dx = A*dz + B*x + D
   f.coef[c] = k1;                                    // A
   f.coef[C + c] = -k1 * k3 * is;                     // B
-  f.coef[2 * C + c] = -k1 * k2 + k1 * k3 * is * f.mean[c];  // D
+  f.coef[2 * C + c] = -k1 * k2 + k1 * k3 * is * p.mean;  // D
+}
+
+template <int NT, bool ATOMIC = false>
+__device__ __forceinline__ void fwd_finalize(const float* psum, const float* psq, int nblk, const FwdFin& f,
+                                             const FwdPar& p) {
+  double S, Q;  // level-2 partials per channel, summed in fp64
+  if (!fin_sum2<NT, ATOMIC>(psum, psq, nblk, f.C, S, Q)) return;
+  fwd_finish(f, blockIdx.x * 64 + (threadIdx.x & 63), S, Q, p);
+}
+
+template <int NT, bool ATOMIC = false>
+__device__ __forceinline__ void bwd_finalize(const float* pdz, const float* pdzx, int nblk, const BwdFin& f,
+                                             const BwdPar& p) {
+  double A, B;
+  if (!fin_sum2<NT, ATOMIC>(pdz, pdzx, nblk, f.C, A, B)) return;
+  bwd_finish(f, blockIdx.x * 64 + (threadIdx.x & 63), A, B, p);
 }
 
 // Level-1 -> level-2 reduce and the finalize in ONE launch: grid (ceil(C/64), S), every block reduces its 64 partial
@@ -277,6 +336,25 @@ __device__ __forceinline__ void bwd_finalize(const float* pdz, const float* pdzx
 // last arriver before the workgroup reads.  Counters start at zero (allocated zeroed) and the last arriver resets
 // its own; launches that share a counter array are stream-ordered.  Saves a launch boundary and the separate
 // finalize pass's own ramp per BatchNorm direction (106 per ResNet-50 step).
+// l1_rows<NT> with every load unconditional: a buffer over the split's rows b0 .. b1 - 1, so a row past b1 lies past
+// its end and reads as +0 (a channel past C is sent there too).  Same values, same order, one round trip where the
+// predicated loads of l1_rows compile to three
+template <int NT>
+__device__ __forceinline__ float l1_rows_buf(const float* __restrict__ src, int b0, int b1, int C, int c, int lane) {
+  constexpr int G = NT / 64, U = kRowsPerSplit / G;
+  const int bytes = (b1 - b0) * C * (int)sizeof(float);
+  const __amdgpu_buffer_rsrc_t r = buf_rsrc(src + (int64_t)b0 * C, bytes);
+  float x[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+    x[u] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
+        r, c < C ? ((lane + u * G) * C + c) * (int)sizeof(float) : bytes, 0, 0));
+  float a = 0.f;
+#pragma unroll
+  for (int u = 0; u < U; ++u) a += x[u];
+  return a;
+}
+
 template <int NT>
 __device__ __forceinline__ bool reduce_l2_last(const float* __restrict__ part, int nblk, int C, float* l2, int S,
                                                unsigned* cnt) {
@@ -289,11 +367,8 @@ __device__ __forceinline__ bool reduce_l2_last(const float* __restrict__ part, i
   const int b0 = s * kRowsPerSplit;
   int b1 = b0 + kRowsPerSplit;
   if (b1 > nblk) b1 = nblk;
-  float a0 = 0.f, a1 = 0.f;
-  if (c < C) {
-    a0 = l1_rows<NT>(part, b0, b1, C, c, lane);
-    a1 = l1_rows<NT>(part + (int64_t)nblk * C, b0, b1, C, c, lane);
-  }
+  const float a0 = l1_rows_buf<NT>(part, b0, b1, C, c, lane);
+  const float a1 = l1_rows_buf<NT>(part + (int64_t)nblk * C, b0, b1, C, c, lane);
   sh[0][threadIdx.x] = a0;
   sh[1][threadIdx.x] = a1;
   __syncthreads();
@@ -328,15 +403,126 @@ constexpr int kFinNT = 1024;
 template <int NT>
 __global__ __launch_bounds__(NT) void bn_fwd_reduce_finalize_kernel(const float* __restrict__ part, int nblk, float* l2,
                                                                     int S, unsigned* cnt, FwdFin f) {
+  // the finalizing threads of the last arriver are the first wave's; every block loads for them, which block is last
+  // is not known yet
+  const int c = blockIdx.x * 64 + (threadIdx.x & 63);
+  const FwdPar p = fwd_params(f, c, threadIdx.x < 64 && c < f.C);
   if (!reduce_l2_last<NT>(part, nblk, f.C, l2, S, cnt)) return;
-  fwd_finalize<NT, true>(l2, l2 + (int64_t)S * f.C, S, f);
+  fwd_finalize<NT, true>(l2, l2 + (int64_t)S * f.C, S, f, p);
 }
 
 template <int NT>
 __global__ __launch_bounds__(NT) void bn_bwd_reduce_finalize_kernel(const float* __restrict__ part, int nblk, float* l2,
                                                                     int S, unsigned* cnt, BwdFin f) {
+  const int c = blockIdx.x * 64 + (threadIdx.x & 63);
+  const BwdPar p = bwd_params(f, c, threadIdx.x < 64 && c < f.C);
   if (!reduce_l2_last<NT>(part, nblk, f.C, l2, S, cnt)) return;
-  bwd_finalize<NT, true>(l2, l2 + (int64_t)S * f.C, S, f);
+  bwd_finalize<NT, true>(l2, l2 + (int64_t)S * f.C, S, f, p);
+}
+
+// ---- reduce + finalize in ONE workgroup per CW channels, for the BatchNorms with few partial rows (nblk <= kFinSingleMax:
+// the 14x14 and 7x7 stages of ResNet-50, 28 of its 53 BatchNorms).  There the ticket kernels above join only 2-7
+// workgroups, yet pay for it with the level-2 stores, their drain, the ticket's atomic and the re-read of the rows:
+// four dependent memory round trips that move almost no data.  Here every thread issues all of its level-1 loads of
+// both sums (and wave 0 the per-channel parameters) before its first wait, the rest happens in LDS, and nothing but
+// the outputs is written: no counters, no level-2 rows, no atomics.
+//
+// The summation tree is the ticket path's, so every output is bit-identical to it:
+//   per split s of 64 rows, lane group g = 0..15 sums rows g, g + 16, g + 32, g + 48 in that order (l1_rows<kFinNT>),
+//   the 16 group sums are added in group order (fp32): the level-2 value r_s;
+//   fin_sum2<kFinNT> then adds r_0 .. r_{S-1} in order in fp64 (S <= 16: one row per lane group, groups in order).
+// Thread t = j * CW + lc serves channel lc of the workgroup, lane group g = j % 16 and the splits sub, sub + NSUB, ...
+// (sub = j / 16, NSUB = 64 / CW): a narrower workgroup spreads a BatchNorm over more CUs (C = 256 at CW = 64 is four
+// workgroups, each pulling 200 KB through one CU's L2 port) and leaves each thread fewer rows, while a wave still
+// reads 64 / CW whole rows of CW contiguous floats per instruction.
+constexpr int kFinSingleSplits = 8;                               // splits of 64 rows one workgroup holds in flight
+constexpr int kFinSingleMax = kFinSingleSplits * kRowsPerSplit;   // = 512 rows: 32 rows x 2 sums per thread at CW = 64
+
+// SM: the splits the workgroup covers (>= S).  A row past nblk or a channel past C is read past the end of the buffer
+// descriptor and comes back as +0 (buf_rsrc): every load is unconditional.
+// load_params: the caller's parameter loads, issued behind the row loads (ahead of them the row offsets' 64-bit
+// multiply-adds picked a parameter's register as their don't-care high half, and waited for it)
+template <int CW, int SM, typename F>
+__device__ __forceinline__ bool single_sum2(const float* __restrict__ part, int nblk, int C, double& A, double& B,
+                                            F&& load_params) {
+  constexpr int NT = kFinNT;
+  constexpr int NSUB = 64 / CW;      // split lanes: thread groups that share (channel, lane group), each SM / NSUB splits
+  constexpr int KS = SM / NSUB;      // splits per thread
+  constexpr int RS = CW == 64 && SM > 4 ? 4 : SM;  // splits per LDS round: sh stays at 32 KB
+  static_assert(NT / CW == 16 * NSUB && SM % NSUB == 0 && SM % RS == 0 && 2 * RS * CW <= NT && SM <= 16, "mapping");
+  __shared__ float sh[2][RS][16][CW];
+  __shared__ float rs[2][SM][CW];
+  const int t = threadIdx.x;
+  const int lc = t % CW, j = t / CW, g = j & 15, sub = j >> 4;
+  const int c = blockIdx.x * CW + lc;
+  const int bytes = 2 * nblk * C * (int)sizeof(float);  // < 2^31: fin_path
+  const __amdgpu_buffer_rsrc_t src = buf_rsrc(part, bytes);
+  float x[2][KS][4];
+#pragma unroll
+  for (int w = 0; w < 2; ++w)
+#pragma unroll
+    for (int k = 0; k < KS; ++k)
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int b = (sub + NSUB * k) * kRowsPerSplit + g + 16 * u;
+        const int off = ((w * nblk + b) * C + c) * (int)sizeof(float);
+        x[w][k][u] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(src, b < nblk && c < C ? off : bytes, 0, 0));
+      }
+  load_params();
+  // all of them are issued before anything waits: left alone the scheduler pulls the first round's LDS writes, and the
+  // waits they need, in between the loads (two to three round trips instead of one)
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int r0 = 0; r0 < SM; r0 += RS) {
+    if (r0 != 0) __syncthreads();  // the previous round's sh has been read
+#pragma unroll
+    for (int w = 0; w < 2; ++w)
+#pragma unroll
+      for (int k = 0; k < KS; ++k) {
+        float a = 0.f;  // l1_rows: rows in order
+#pragma unroll
+        for (int u = 0; u < 4; ++u) a += x[w][k][u];
+        const int s = sub + NSUB * k;  // CW = 64: sub = 0, so the round test folds away
+        if (s >= r0 && s < r0 + RS) sh[w][s - r0][g][lc] = a;
+      }
+    __syncthreads();
+    if (t < 2 * RS * CW) {  // one (sum, split, channel) per thread: the 16 group sums in group order
+      const int w = t / (RS * CW), sl = t / CW % RS;
+      float r = 0.f;
+#pragma unroll
+      for (int gg = 0; gg < 16; ++gg) r += sh[w][sl][gg][lc];
+      rs[w][r0 + sl][lc] = r;
+    }
+  }
+  __syncthreads();
+  if (t >= CW || c >= C) return false;
+  // fin_sum2 over S <= 16 level-2 rows: r_0 .. r_{S-1} in order; the splits past S are +0 and change nothing
+  double sa = 0.0, sb = 0.0;
+#pragma unroll
+  for (int s = 0; s < SM; ++s) { sa += (double)rs[0][s][t]; sb += (double)rs[1][s][t]; }
+  A = sa;
+  B = sb;
+  return true;
+}
+
+template <int CW, int SM>
+__global__ __launch_bounds__(kFinNT) void bn_fwd_finalize_single_kernel(const float* __restrict__ part, int nblk,
+                                                                        FwdFin f) {
+  const int c = blockIdx.x * CW + threadIdx.x % CW;
+  FwdPar p;
+  double S, Q;
+  if (!single_sum2<CW, SM>(part, nblk, f.C, S, Q, [&] { p = fwd_params(f, c, threadIdx.x < CW && c < f.C); })) return;
+  fwd_finish(f, c, S, Q, p);
+}
+
+template <int CW, int SM>
+__global__ __launch_bounds__(kFinNT) void bn_bwd_finalize_single_kernel(const float* __restrict__ part, int nblk,
+                                                                        BwdFin f) {
+  const int c = blockIdx.x * CW + threadIdx.x % CW;
+  BwdPar p;
+  double A, B;
+  if (!single_sum2<CW, SM>(part, nblk, f.C, A, B, [&] { p = bwd_params(f, c, threadIdx.x < CW && c < f.C); })) return;
+  bwd_finish(f, c, A, B, p);
 }
 
 template <int NT>
@@ -664,11 +850,32 @@ inline void launch_apply(hipStream_t stream, int64_t n_vec, int G, const void* x
                      (bf16x8*)y, scale, bias, n_vec, G, mask, rsb);
 }
 
-// level-1 partials [2][nblk][C] -> finalize: one fused launch with a counter array (>= ceil(C/64) zeroed words),
-// else the reduce and finalize kernels back to back
+// A/B knob (PLX_BN_FIN_SINGLE, plx_bn_set_fin_single): 1 = a one-launch reduce + finalize over at most kFinSingleMax
+// partial rows runs in single workgroups (bn_*_finalize_single_kernel), 0 = every one takes the ticket kernels
+int g_bn_fin_single = 1;
+
+// Which kernels a reduce + finalize over nblk partial rows runs: 0 = reduce and finalize back to back (no counters),
+// 1 = the ticket kernel, 2 = the single-workgroup kernel
+enum { kFinTwoLaunch = 0, kFinTicket = 1, kFinSingle = 2 };
+
+inline int fin_path(int nblk, int C, bool counters) {
+  if (!counters) return kFinTwoLaunch;
+  // the single kernel addresses the partials with 32-bit byte offsets: [2][nblk][C] floats below 2 GiB
+  return g_bn_fin_single && nblk <= kFinSingleMax && (int64_t)nblk * C < (1 << 28) ? kFinSingle : kFinTicket;
+}
+
+// level-1 partials [2][nblk][C] -> finalize: one fused launch with a counter array (>= ceil(C/64) zeroed words; the
+// single-workgroup kernel leaves it and the level-2 rows `l2` untouched), else the reduce and finalize kernels back
+// to back
 inline void reduce_finalize_fwd(hipStream_t stream, const float* part, int nblk, float* l2, unsigned* cnt,
                                 const FwdFin& f) {
   const int C = f.C, S = (nblk + kRowsPerSplit - 1) / kRowsPerSplit;
+  if (fin_path(nblk, C, cnt != nullptr) == kFinSingle) {
+    // two splits (the 7x7 stage's 98 rows) or all eight in flight; 64 channels per workgroup
+    auto k = S <= 2 ? bn_fwd_finalize_single_kernel<64, 2> : bn_fwd_finalize_single_kernel<64, kFinSingleSplits>;
+    hipLaunchKernelGGL(k, dim3((C + 63) / 64), dim3(kFinNT), 0, stream, part, nblk, f);
+    return;
+  }
   if (cnt != nullptr) {
     hipLaunchKernelGGL(bn_fwd_reduce_finalize_kernel<kFinNT>, dim3((C + 63) / 64, S), dim3(kFinNT), 0, stream, part, nblk, l2, S,
                        cnt, f);
@@ -685,6 +892,12 @@ inline void reduce_finalize_fwd(hipStream_t stream, const float* part, int nblk,
 inline void reduce_finalize_bwd(hipStream_t stream, const float* part, int nblk, float* l2, unsigned* cnt,
                                 const BwdFin& f) {
   const int C = f.C, S = (nblk + kRowsPerSplit - 1) / kRowsPerSplit;
+  if (fin_path(nblk, C, cnt != nullptr) == kFinSingle) {
+    // two splits (the 7x7 stage's 98 rows) or all eight in flight; 64 channels per workgroup
+    auto k = S <= 2 ? bn_bwd_finalize_single_kernel<64, 2> : bn_bwd_finalize_single_kernel<64, kFinSingleSplits>;
+    hipLaunchKernelGGL(k, dim3((C + 63) / 64), dim3(kFinNT), 0, stream, part, nblk, f);
+    return;
+  }
   if (cnt != nullptr) {
     hipLaunchKernelGGL(bn_bwd_reduce_finalize_kernel<kFinNT>, dim3((C + 63) / 64, S), dim3(kFinNT), 0, stream, part, nblk, l2, S,
                        cnt, f);
@@ -1199,6 +1412,17 @@ inline dim3 stem_bwd_grid(int N, int H, int W, int G, bool dx) {
 
 // A/B knob: 1 (default) = the thinned stem kernels, 0 = their predecessors (g_bn_thin)
 PLX_API void plx_bn_set_thin(int on) { g_bn_thin = on != 0; }
+
+// A/B knob: 1 (default) = single-workgroup reduce + finalize for few partial rows, 0 = the ticket kernels throughout
+PLX_API void plx_bn_set_fin_single(int on) { g_bn_fin_single = on != 0; }
+
+// Host only: the kernels that the reduce + finalize of a call WITH a counter array runs for nblk partial rows of C
+// channels under the current switch: 1 = the ticket kernel, 2 = the single-workgroup kernel (-1: not a valid call).
+// A call without counters always runs the reduce and the finalize kernel back to back.
+PLX_API int plx_bn_fin_path(int nblk, int C) {
+  if (nblk < 1 || C < 8 || C % 8 || ((C / 8) & (C / 8 - 1))) return -1;
+  return fin_path(nblk, C, true);
+}
 
 // fp32 workspace of a call that runs its own statistics / reduce pass: level-1 [2][nblk][C] + level-2 [2][S][C].
 PLX_API int64_t plx_bn_workspace(int64_t M, int C) {

@@ -197,6 +197,8 @@ def lib(name: str) -> ctypes.CDLL:
             handle.plx_set_tn_atomic(int(os.environ["PLX_WGRAD_ATOMIC"]))
         if name == "plx_bn" and os.environ.get("PLX_BN_THIN"):  # A/B knob: 0 = the kernels before the thinned ones
             handle.plx_bn_set_thin(int(os.environ["PLX_BN_THIN"]))
+        if name == "plx_bn" and os.environ.get("PLX_BN_FIN_SINGLE"):  # A/B knob: 0 = the ticket kernels throughout
+            handle.plx_bn_set_fin_single(int(os.environ["PLX_BN_FIN_SINGLE"]))
         if name == "plx_gemm" and os.environ.get("PLX_GEMM_WAVES"):  # 8 = ping-pong kernel, 4 = AGPR 4-wave kernel
             handle.plx_gemm256_set_waves(int(os.environ["PLX_GEMM_WAVES"]))
         _loaded[name] = handle
@@ -234,6 +236,8 @@ SIGNATURES: Dict[str, Dict[str, list]] = {
     },
     "plx_bn": {
         "plx_bn_set_thin": [_I],
+        "plx_bn_set_fin_single": [_I],
+        "plx_bn_fin_path": [_I, _I],
         "plx_bn_workspace": [_L, _I],
         "plx_bn_args_size": [_I],
         "plx_bn_forward": [_P, _P],  # (BnForwardArgs*, stream)
