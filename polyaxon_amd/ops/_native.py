@@ -26,6 +26,10 @@ ROCM = Path(os.environ.get("ROCM_PATH", "/opt/rocm"))
 # name -> (sources, kind, extra link flags)
 LIBRARIES: Dict[str, dict] = {
     "plx_train": {"sources": ["train_kernels.hip"], "kind": "hip", "link": []},
+    # a library of its own: built without packed fp32 arithmetic, a flag the other libraries' kernels were not
+    # measured under (plx_train stays byte for byte what it was)
+    "plx_layerwise": {"sources": ["layerwise_kernels.hip"], "kind": "hip", "link": [],
+                      "flags": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]},
     "plx_polytune": {"sources": ["polytune_kernels.hip"], "kind": "hip", "link": []},
     "plx_bn": {"sources": ["bn_kernels.hip"], "kind": "hip", "link": []},
     "plx_procmon": {"sources": ["procmon.cpp"], "kind": "cpp", "link": ["-lpthread"]},
@@ -76,7 +80,7 @@ def build(name: str, force: bool = False, verbose: bool = False) -> Path:
     """Compile one library if its sources changed. Returns the .so path."""
     spec = LIBRARIES[name]
     srcs = [CSRC / s for s in spec["sources"]]
-    flags = _flags(spec["kind"])
+    flags = _flags(spec["kind"]) + spec.get("flags", [])
     out = lib_path(name)
     stamp = out.with_suffix(".so.sha")
     digest = _digest(srcs, flags + spec["link"])
@@ -108,7 +112,8 @@ def _stale(name: str) -> bool:
     if not stamp.exists():
         return False  # shipped without a stamp: trust it
     try:
-        digest = _digest([CSRC / s for s in spec["sources"]], _flags(spec["kind"]) + spec["link"])
+        digest = _digest([CSRC / s for s in spec["sources"]],
+                         _flags(spec["kind"]) + spec.get("flags", []) + spec["link"])
     except OSError:
         return False
     return stamp.read_text().strip() != digest
@@ -233,6 +238,12 @@ SIGNATURES: Dict[str, Dict[str, list]] = {
         "plx_synth_images": [_P, _P, _I, _I, _I, _P, _I, _I, _F, _U64, _P, _P],
         "plx_set_adamw_grid_cap": [_I],
         "plx_set_adamw_wide": [_I],
+    },
+    "plx_layerwise": {
+        "plx_lw_chunk": [],
+        "plx_lw_norms": [_I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P],
+        "plx_lw_ratios": [_I, _P, _P, _P, _I, _P, _P, _P, _P],
+        "plx_lw_update": [_I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P],
     },
     "plx_bn": {
         "plx_bn_set_thin": [_I],

@@ -16,6 +16,10 @@ warm-up, horizon, floor, decay) that ``plx_lr_schedule`` turns into ``hp[0]`` fr
 launch ahead of the step's optimizer launches.  A trial changes its schedule -- kind included -- with one more
 32-byte copy; snapshots restore the step counter, so a resumed trial continues its curve with nothing else saved.
 
+Layer-wise trust ratios (``FusedSGD(trust_coef=)``: LARS; ``FusedAdamW(lamb=True)``: LAMB; opt-in) keep to it as
+well: the per-tensor norms, the ratios and the update are three launches over a chunk table built once
+(csrc/layerwise_kernels.hip), in a fixed summation order, and ``trust_coef`` is one more slot of the tensor.
+
 On CPU (no native library) the same update is computed with torch ops; tests compare the two.
 """
 from __future__ import annotations
@@ -171,6 +175,110 @@ class _Clipping:
         return self._need_clip().stats()
 
 
+class _LayerNorms:
+    """The device side of the layer-wise trust ratios (``FusedSGD(trust_coef=)``: LARS; ``FusedAdamW(lamb=True)``:
+    LAMB; csrc/layerwise_kernels.hip).  The decay segments -- every tensor of rank 2 or higher -- are cut into chunks
+    of ``plx_lw_chunk()`` elements that never cross a segment: per chunk [lo, hi) and its segment, per segment its
+    first chunk and chunk count.  A step is three launches over that table: two sums of squares per chunk
+    (``plx_lw_norms``; LAMB's also advances and stores the moments), one ratio per segment (``plx_lw_ratios``), the
+    update of every chunk with its segment's ratio (``plx_lw_update``).  The padding after a segment's ``numel`` is
+    in no chunk: it is in no norm and is never written.  The 1-D tail keeps the plain update.  No host sync, no
+    atomics, a fixed summation order; every buffer is allocated here, never during a capture."""
+
+    LARS, LAMB, LAMB_LP = 0, 1, 2
+
+    def __init__(self, flat: FlatParams, mode: int):
+        self.flat = flat
+        self.mode = mode
+        self.segs = [s for s in flat.segments if s.decay]
+        if not flat.params.is_cuda:
+            return
+        chunk = _native.lib("plx_layerwise").plx_lw_chunk()
+        lo, hi, seg, first, count = [], [], [], [], []
+        for i, s in enumerate(self.segs):
+            end = s.offset + s.numel
+            first.append(len(lo))
+            for c in range(s.offset, end, chunk):
+                lo.append(c)
+                hi.append(min(c + chunk, end))
+                seg.append(i)
+            count.append(len(lo) - first[-1])
+        dev = flat.device
+        self.n_chunks, self.n_segs = len(lo), len(self.segs)
+        self.chunk_lo = torch.tensor(lo, dtype=torch.int64, device=dev)
+        self.chunk_hi = torch.tensor(hi, dtype=torch.int64, device=dev)
+        self.chunk_seg = torch.tensor(seg, dtype=torch.int32, device=dev)
+        self.seg_first = torch.tensor(first, dtype=torch.int32, device=dev)
+        self.seg_count = torch.tensor(count, dtype=torch.int32, device=dev)
+        self.partials = torch.zeros(2 * max(self.n_chunks, 1), dtype=torch.float32, device=dev)
+        self.ratio = torch.ones(max(self.n_segs, 1), dtype=torch.float32, device=dev)
+
+    def step(self, m: torch.Tensor, v: Optional[torch.Tensor], hp: torch.Tensor, step: torch.Tensor,
+             clip: Optional[_GradClip], stream: int) -> None:
+        """Queue the three passes over the decay segments on ``stream`` (GPU).  ``m``: the momentum buffer (LARS) or
+        ``exp_avg``; ``v``: ``exp_avg_sq`` (LAMB).  ``clip``: its state must already be this step's."""
+        f, lib = self.flat, _native.lib("plx_layerwise")
+        side_stream.join(f.device)  # the norm pass reads every gradient slot (as _GradClip.measure)
+        lp = self.mode == self.LAMB_LP
+        g = (f.lp_grads if lp else f.grads).data_ptr()
+        vp = v.data_ptr() if v is not None else None
+        state = clip.state.data_ptr() if clip is not None else None
+        _native.check(lib.plx_lw_norms(self.mode, f.params.data_ptr(), g, m.data_ptr(), vp, self.chunk_lo.data_ptr(),
+                                       self.chunk_hi.data_ptr(), self.n_chunks, hp.data_ptr(), step.data_ptr(), state,
+                                       self.partials.data_ptr(), stream), "plx_lw_norms")
+        _native.check(lib.plx_lw_ratios(int(self.mode != self.LARS), self.partials.data_ptr(),
+                                        self.seg_first.data_ptr(), self.seg_count.data_ptr(), self.n_segs,
+                                        hp.data_ptr(), state, self.ratio.data_ptr(), stream), "plx_lw_ratios")
+        _native.check(lib.plx_lw_update(self.mode, f.params.data_ptr(), g, m.data_ptr(), vp,
+                                        f.lp_params.data_ptr() if lp else None, self.chunk_lo.data_ptr(),
+                                        self.chunk_hi.data_ptr(), self.chunk_seg.data_ptr(), self.n_chunks,
+                                        self.ratio.data_ptr(), hp.data_ptr(), step.data_ptr(), state, stream),
+                      "plx_lw_update")
+
+    def spans(self):
+        """(lo, hi) of every decay segment's real elements (the CPU twins)."""
+        return [(s.offset, s.offset + s.numel) for s in self.segs]
+
+
+class _Layerwise:
+    """The layer-wise surface the fused optimizers share.  Off (default): nothing exists -- no table, no buffer, the
+    launches are the ones without it.  On, a bucket can cut a segment, so the per-bucket updates
+    (``step_range_``, ``FlatDDP(optimizer=...)``, ZeRO-1) cannot see a whole norm and are refused."""
+
+    _lw: Optional[_LayerNorms] = None
+    _in_backward = False
+
+    def _init_layerwise(self, flat: FlatParams, mode: Optional[int], key: Optional[str] = None) -> None:
+        if mode is None:
+            return
+        if key is not None:  # a hyper-parameter of its own, in the hp slot after max_grad_norm's
+            if len(self.HP) == _GradClip.SLOT:
+                self.HP = self.HP + ("_slot5",)  # no clipping: slot 5 stays 0 and `key` still lands in slot 6
+            self.HP = self.HP + (key,)  # this instance only
+        self._lw = _LayerNorms(flat, mode)
+
+    @property
+    def layerwise(self) -> bool:
+        return self._lw is not None
+
+    def _no_ranges(self, what: str) -> None:
+        if self._lw is not None:
+            raise ValueError(f"a layer-wise optimizer (LARS / LAMB) needs every segment's whole norm before any "
+                             f"update: it has no {what} (step_range_, FlatDDP(optimizer=...), ZeRO-1)")
+
+    # set by FlatDDP(optimizer=...): the update runs per gradient bucket during the backward (step_range_), and
+    # step_() only closes the step's bookkeeping
+    @property
+    def in_backward(self) -> bool:
+        return self._in_backward
+
+    @in_backward.setter
+    def in_backward(self, on: bool) -> None:
+        if on:
+            self._no_ranges("per-bucket update inside the backward")
+        self._in_backward = bool(on)
+
+
 def lr_factor(kind, s, W, T, m, gamma, E) -> torch.Tensor:
     """The factor ``plx_lr_schedule`` multiplies the base LR by at ``s`` completed steps, in torch float32 (the CPU
     path, and the twin the tests hold the kernel against).  ``kind``: a name or code of ops/lr_schedule.py KINDS;
@@ -279,18 +387,23 @@ class _Scheduled:
         return self.hp[0]
 
 
-class FusedSGD(_Clipping, _Scheduled):
-    """SGD with momentum / nesterov / dampening and weight decay on the decay segment only."""
+class FusedSGD(_Clipping, _Layerwise, _Scheduled):
+    """SGD with momentum / nesterov / dampening and weight decay on the decay segment only; with ``trust_coef`` LARS:
+    per decay segment r = trust_coef |w| / (|g| + wd |w| + 1e-8) (1 unless both norms are positive) scales
+    d = r (g + wd w) ahead of the momentum rule."""
 
     HP = ("lr", "momentum", "weight_decay", "nesterov", "dampening")
 
     def __init__(self, flat: FlatParams, lr: float = 0.1, momentum: float = 0.9, weight_decay: float = 1e-4,
                  nesterov: bool = False, dampening: float = 0.0, step_counter: Optional[torch.Tensor] = None,
-                 max_grad_norm: Optional[float] = None, lr_schedule: Optional[str] = None):
+                 max_grad_norm: Optional[float] = None, lr_schedule: Optional[str] = None,
+                 trust_coef: Optional[float] = None):
         """``max_grad_norm``: a number enables global-norm gradient clipping for the optimizer's lifetime (a device
         hyper-parameter like the others; 0 = measure the norm, no limit); None: no clipping at all.
         ``lr_schedule``: a kind name (ops/lr_schedule.py KINDS) enables the device-resident LR schedule for the
-        optimizer's lifetime, ``lr`` being its base LR; None: constant ``lr``, no schedule at all."""
+        optimizer's lifetime, ``lr`` being its base LR; None: constant ``lr``, no schedule at all.
+        ``trust_coef``: a number enables LARS on the decay segments for the optimizer's lifetime (a device
+        hyper-parameter like the others, hp slot 6); None: plain SGD, nothing of it exists."""
         self.flat = flat
         dev = flat.device
         self.momentum_buf = torch.zeros_like(flat.params)
@@ -298,9 +411,11 @@ class FusedSGD(_Clipping, _Scheduled):
         # step counter shared with the metric ring: 0 right after reset() => momentum := grad
         self.step = step_counter if step_counter is not None else torch.zeros(1, dtype=torch.int32, device=dev)
         self._init_clip(flat, max_grad_norm)
+        self._init_layerwise(flat, None if trust_coef is None else _LayerNorms.LARS, "trust_coef")
         sched = self._init_sched(flat, lr_schedule)
         self.set_hparams(lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=nesterov,
-                         dampening=dampening, **({"max_grad_norm": max_grad_norm} if self.clipping else {}), **sched)
+                         dampening=dampening, **({"max_grad_norm": max_grad_norm} if self.clipping else {}),
+                         **({"trust_coef": trust_coef} if self.layerwise else {}), **sched)
 
     def set_hparams(self, **hp) -> None:
         self._set_hparams("SGD", hp)
@@ -322,6 +437,8 @@ class FusedSGD(_Clipping, _Scheduled):
         self._schedule_lr()  # hp[0] of this step, ahead of the norm pass and the update
         if not f.params.is_cuda:
             self._step_reference()
+        elif self._lw is not None:
+            self._step_layerwise(_stream_ptr(f.params))
         elif self._clip is not None:
             st = _stream_ptr(f.params)
             self._clip.measure(self.hp, st)
@@ -335,6 +452,24 @@ class FusedSGD(_Clipping, _Scheduled):
                 self.hp.data_ptr(), self.step.data_ptr(), _stream_ptr(f.params))
             _native.check(rc, "plx_sgd_flat")
 
+    def _step_layerwise(self, st: int) -> None:
+        """LARS: [norm pass + finalize of the clip,] the three layer-wise passes over the decay segments, and the
+        plain launch (``n_decay`` 0) over the 1-D tail, all on the current stream."""
+        f, lib = self.flat, _native.lib("plx_train")
+        if self._clip is not None:
+            self._clip.measure(self.hp, st)
+        self._lw.step(self.momentum_buf, None, self.hp, self.step, self._clip, st)
+        nd = f.n_decay
+        if f.numel > nd:
+            p, g, m = (t.data_ptr() + 4 * nd for t in (f.params, f.grads, self.momentum_buf))
+            if self._clip is not None:
+                _native.check(lib.plx_sgd_flat_clip(p, g, m, f.numel - nd, 0, self.hp.data_ptr(),
+                                                    self.step.data_ptr(), self._clip.state.data_ptr(), st),
+                              "plx_sgd_flat_clip")
+            else:
+                _native.check(lib.plx_sgd_flat(p, g, m, f.numel - nd, 0, self.hp.data_ptr(), self.step.data_ptr(),
+                                               st), "plx_sgd_flat")
+
     @torch.no_grad()
     def _step_reference(self) -> None:
         f = self.flat
@@ -347,6 +482,12 @@ class FusedSGD(_Clipping, _Scheduled):
                 return
             g.mul_(scale)  # a rounding step of its own, before weight decay (torch's order)
         g[: f.n_decay] += wd * f.params[: f.n_decay]
+        if self._lw is not None:  # LARS: d = r (g + wd w) per decay segment
+            tc = self.hp[6]
+            for lo, hi in self._lw.spans():
+                wn, gn = f.params[lo:hi].norm(), f.grads[lo:hi].mul(1.0 if self._clip is None else scale).norm()
+                if float(wn) > 0.0 and float(gn) > 0.0:
+                    g[lo:hi] *= tc * wn / (gn + wd * wn + 1e-8)
         if int(self.step.item()) == 0:
             self.momentum_buf.copy_(g)
         else:
@@ -359,13 +500,19 @@ class FusedSGD(_Clipping, _Scheduled):
         return {"momentum": self.momentum_buf}
 
 
-class FusedAdamW(_Clipping, _Scheduled):
+class FusedAdamW(_Clipping, _Layerwise, _Scheduled):
+    """AdamW with decoupled weight decay on the decay segment only; with ``lamb=True`` LAMB: the moments and bias
+    correction are AdamW's, u = m^/(sqrt(v^) + eps) + wd w, and per decay segment r = |w| / |u| (1 unless both norms
+    are positive) scales the step, w -= lr r u."""
+
     HP = ("lr", "beta1", "beta2", "eps", "weight_decay")
 
     def __init__(self, flat: FlatParams, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 1e-2, step_counter: Optional[torch.Tensor] = None,
-                 max_grad_norm: Optional[float] = None, lr_schedule: Optional[str] = None):
-        """``max_grad_norm``: a number enables global-norm gradient clipping for the optimizer's lifetime (a device
+                 max_grad_norm: Optional[float] = None, lr_schedule: Optional[str] = None, lamb: bool = False):
+        """``lamb``: LAMB on the decay segments for the optimizer's lifetime (fp32 and lp mode; no hyper-parameter
+        of its own); it excludes the per-bucket updates like clipping does.
+        ``max_grad_norm``: a number enables global-norm gradient clipping for the optimizer's lifetime (a device
         hyper-parameter like the others; 0 = measure the norm, no limit); None: no clipping at all.  Clipping needs
         the whole gradient before any update, so it excludes the per-bucket updates (``step_range_``,
         ``FlatDDP(optimizer=...)``).
@@ -379,6 +526,8 @@ class FusedAdamW(_Clipping, _Scheduled):
         self.hp = torch.zeros(8, dtype=torch.float32, device=dev)
         self.step = step_counter if step_counter is not None else torch.zeros(1, dtype=torch.int32, device=dev)
         self._init_clip(flat, max_grad_norm)
+        if lamb:
+            self._init_layerwise(flat, _LayerNorms.LAMB if flat.lp_params is None else _LayerNorms.LAMB_LP)
         sched = self._init_sched(flat, lr_schedule)
         self.set_hparams(lr=lr, beta1=betas[0], beta2=betas[1], eps=eps, weight_decay=weight_decay,
                          **({"max_grad_norm": max_grad_norm} if self.clipping else {}), **sched)
@@ -396,16 +545,13 @@ class FusedAdamW(_Clipping, _Scheduled):
         """ZeRO-1 (FlatDDP(shard_optimizer=True)): keep the moments only for the ``numel`` flat elements this rank
         updates, packed; every update then names its range's offset in that packed state (``step_range_(state_off=)``).
         The full-size moments are released."""
+        self._no_ranges("sharded state")
         dev = self.flat.device
         self.exp_avg = torch.zeros(numel, dtype=torch.float32, device=dev)
         self.exp_avg_sq = torch.zeros(numel, dtype=torch.float32, device=dev)
         self.sharded = True
 
     sharded = False
-
-    # set by FlatDDP(optimizer=...): the update runs per gradient bucket during the backward (step_range_), and
-    # step_() only closes the step's bookkeeping
-    in_backward = False
 
     def step_(self) -> None:
         f = self.flat
@@ -422,6 +568,9 @@ class FusedAdamW(_Clipping, _Scheduled):
             return
         lib = _native.lib("plx_train")
         st = _stream_ptr(f.params)
+        if self._lw is not None:
+            self._step_layerwise(lib, st)
+            return
         if self._clip is not None:
             self._step_clipped(lib, st)
             return
@@ -465,6 +614,24 @@ class FusedAdamW(_Clipping, _Scheduled):
                 f.params.data_ptr() + off, f.grads.data_ptr(), self.exp_avg.data_ptr() + off,
                 self.exp_avg_sq.data_ptr() + off, f.numel - nd, 0, hp, step, state, st), "plx_adamw_flat_clip")
 
+    def _step_layerwise(self, lib, st: int) -> None:
+        """LAMB: [norm pass + finalize of the clip,] the three layer-wise passes over the decay segments, and the
+        plain AdamW launch (``n_decay`` 0) over the 1-D tail, all on the current stream."""
+        f, clip = self.flat, self._clip
+        if clip is not None:
+            clip.measure(self.hp, st)
+        self._lw.step(self.exp_avg, self.exp_avg_sq, self.hp, self.step, clip, st)
+        nd = f.n_decay
+        if f.numel > nd:
+            off = nd * 4
+            args = (f.params.data_ptr() + off, f.grads.data_ptr() + (0 if f.lp_params is not None else off),
+                    self.exp_avg.data_ptr() + off, self.exp_avg_sq.data_ptr() + off, f.numel - nd, 0,
+                    self.hp.data_ptr(), self.step.data_ptr())
+            if clip is not None:
+                _native.check(lib.plx_adamw_flat_clip(*args, clip.state.data_ptr(), st), "plx_adamw_flat_clip")
+            else:
+                _native.check(lib.plx_adamw_flat(*args, st), "plx_adamw_flat")
+
     def step_range_(self, lo: int, hi: int, stream: Optional[int] = None, state_off: Optional[int] = None) -> None:
         """AdamW over flat elements [lo, hi) on ``stream`` (a FlatDDP bucket: 4-aligned, and in lp mode entirely
         inside the bf16 decay segment or entirely inside the fp32 tail).  The same per-element update as
@@ -473,6 +640,7 @@ class FusedAdamW(_Clipping, _Scheduled):
         if self._clip is not None:
             raise ValueError("max_grad_norm needs the whole gradient before any update: a clipping optimizer has no "
                              "per-range step (step_range_, FlatDDP(optimizer=...), ZeRO-1)")
+        self._no_ranges("per-range step")
         f = self.flat
         so = lo if state_off is None else state_off
         if self._sched is not None and not self._sched.queued:
@@ -517,12 +685,23 @@ class FusedAdamW(_Clipping, _Scheduled):
                 f.zero_grads()
                 return
             g = g * scale  # a rounding step of its own, before the moments
-        f.params[: f.n_decay].mul_(1.0 - lr * wd)
+        nd = f.n_decay if self._lw is None else 0  # LAMB: the decay term is part of u
+        f.params[:nd].mul_(1.0 - lr * wd)
         self.exp_avg.mul_(b1).add_(g, alpha=1 - b1)
         self.exp_avg_sq.mul_(b2).addcmul_(g, g, value=1 - b2)
         bc1, bc2 = 1 - b1 ** t, 1 - b2 ** t
         denom = (self.exp_avg_sq.sqrt() / bc2 ** 0.5).add_(eps)
-        f.params.addcdiv_(self.exp_avg, denom, value=-lr / bc1)
+        if self._lw is None:
+            f.params.addcdiv_(self.exp_avg, denom, value=-lr / bc1)
+        else:  # LAMB: w -= lr r u per decay segment (the padding is not touched), plain AdamW on the 1-D tail
+            u = self.exp_avg / bc1 / denom
+            for lo, hi in self._lw.spans():
+                w = f.params[lo:hi]
+                us = u[lo:hi] + wd * w
+                wn, un = w.norm(), us.norm()
+                r = wn / un if float(wn) > 0.0 and float(un) > 0.0 else 1.0
+                w.sub_(lr * r * us)
+            f.params[f.n_decay:].sub_(lr * u[f.n_decay:])
         f.zero_grads()
         f.sync_lp()
 

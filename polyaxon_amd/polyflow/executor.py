@@ -53,7 +53,7 @@ class ResidentTrialExecutor:
                  ring_size: int = 4096, init_spec: Optional[Callable] = None,
                  lp_dtype: Optional[torch.dtype] = None, clip_grad: bool = False, lr_schedule=False,
                  loss_hparams: bool = False, dropout: bool = False, dropout_seed: int = 0,
-                 attn_dropout: bool = False):
+                 attn_dropout: bool = False, layerwise: bool = False):
         """``lp_dtype`` (the language models, GPU): the model computes from bf16 weights with bf16 gradients and the
         optimizer keeps the fp32 master (ops/flat.py lp mode); every re-init / restore refreshes the bf16 copy.
         ``clip_grad``: global-norm gradient clipping (ops/optim.py) with ``max_grad_norm`` as one more device
@@ -75,7 +75,11 @@ class ResidentTrialExecutor:
         ``attn_dropout``: dropout on the attention probabilities, its rate ``attn_dropout`` one more device
         hyper-parameter (ops/attn_dropout.py): the model's ``set_attn_dropout`` gets a state built on this executor's
         step counter and keyed by ``dropout_seed``; the flash-attention kernels redraw the mask in the forward and the
-        backward.  Independent of ``dropout``; 0 -- bitwise the plain step -- until a trial sets a rate."""
+        backward.  Independent of ``dropout``; 0 -- bitwise the plain step -- until a trial sets a rate.
+        ``layerwise``: layer-wise trust ratios on every weight tensor of rank 2 or higher (ops/optim.py,
+        csrc/layerwise_kernels.hip): ``sgd`` becomes LARS with ``trust_coef`` as one more device hyper-parameter
+        (0.001 until a trial sets one), ``adamw`` becomes LAMB.  The DP step is the whole-gradient one, so a gang
+        is fine; the per-bucket optimizer modes are not."""
         self.device = torch.device(device)
         self.is_cuda = self.device.type == "cuda"
         if channels_last:
@@ -89,9 +93,11 @@ class ResidentTrialExecutor:
         clip = 0.0 if clip_grad else None
         sched = ("constant" if lr_schedule is True else lr_schedule) or None
         if optimizer == "sgd":
-            self.opt = FusedSGD(self.flat, step_counter=self.step, max_grad_norm=clip, lr_schedule=sched)
+            self.opt = FusedSGD(self.flat, step_counter=self.step, max_grad_norm=clip, lr_schedule=sched,
+                                trust_coef=0.001 if layerwise else None)
         elif optimizer == "adamw":
-            self.opt = FusedAdamW(self.flat, step_counter=self.step, max_grad_norm=clip, lr_schedule=sched)
+            self.opt = FusedAdamW(self.flat, step_counter=self.step, max_grad_norm=clip, lr_schedule=sched,
+                                  lamb=bool(layerwise))
         else:
             raise ValueError(f"unknown optimizer {optimizer!r}")
         # off: nothing exists -- no tensor, the plain launches, and set_hparams drops the key

@@ -24,6 +24,11 @@ hyper-parameters of the loss (ops/loss_hp.py), read from device memory by the fu
 until a trial sets them.  The metric the program commits is then the plain NLL, not the training loss, so trials
 with different smoothing stay comparable.
 
+Every built-in program also takes ``params: {layerwise: true}``: layer-wise trust ratios on every weight tensor of
+rank 2 or higher (ops/optim.py, csrc/layerwise_kernels.hip).  The SGD programs (``resnet50``, ``resnet_tiny``,
+``mlp``) then run LARS with ``trust_coef`` as one more per-trial hyper-parameter; the AdamW programs (``gpt2``,
+``gpt2_tiny``) run LAMB, which has none of its own.
+
 ``gpt2`` and ``gpt2_tiny`` also take ``params: {dropout: true, dropout_seed: n}``: residual and embedding dropout
 (ops/dropout.py) with the rate ``dropout`` as a per-trial hyper-parameter, 0 until a trial sets it.  The rate is
 device data and no mask is stored: the step's kernels draw it from the device step counter, so one captured step
@@ -100,6 +105,20 @@ def _with_clip(prog: TrialProgram, clip: bool) -> TrialProgram:
         prog.hp_keys = prog.hp_keys + ("max_grad_norm",)
         prog.info["warm_hparams"] = {**prog.info.get("warm_hparams", {}), "max_grad_norm": 1.0}
         prog.info["clip_grad"] = True
+    return prog
+
+
+def _layerwise(params: Dict[str, Any]) -> bool:
+    return bool(params.get("layerwise", False))
+
+
+def _with_layerwise(prog: TrialProgram, on: bool) -> TrialProgram:
+    """``layerwise`` SGD programs understand ``trust_coef`` and warm up with one set; the AdamW programs run LAMB."""
+    if on:
+        if "momentum" in prog.hp_keys:
+            prog.hp_keys = prog.hp_keys + ("trust_coef",)
+            prog.info["warm_hparams"] = {**prog.info.get("warm_hparams", {}), "trust_coef": 0.001}
+        prog.info["layerwise"] = True
     return prog
 
 
@@ -209,14 +228,15 @@ def _resnet(params: Dict[str, Any], device, tiny: bool) -> TrialProgram:
     model = resnet18ish(num_classes=classes) if tiny else resnet50(num_classes=classes)
     clip = _clip_grad(params)
     ex = ResidentTrialExecutor(model, data, dev, optimizer="sgd", use_graph=bool(params.get("graph", False)),
-                               clip_grad=clip, lr_schedule=_lr_schedule(params), loss_hparams=_loss_hparams(params))
-    return _with_loss_hp(_with_schedule(_with_clip(TrialProgram(
+                               clip_grad=clip, lr_schedule=_lr_schedule(params), loss_hparams=_loss_hparams(params),
+                               layerwise=_layerwise(params))
+    return _with_layerwise(_with_loss_hp(_with_schedule(_with_clip(TrialProgram(
         ex, unit_steps=int(params.get("unit_steps", 1 if tiny else 4)),
         window=int(params.get("window", 4)), hp_keys=("lr", "momentum", "weight_decay", "nesterov"),
         info={"model": "resnet18ish" if tiny else "resnet50", "batch": batch, "image": image,
               "classes": classes, "data": "synthetic, fresh per step (ops/synth.py)",
               "warm_hparams": {"lr": 0.01, "momentum": 0.9, "weight_decay": 1e-4},
-              "images_per_step": batch}), clip), params), _loss_hparams(params))
+              "images_per_step": batch}), clip), params), _loss_hparams(params)), _layerwise(params))
 
 
 def _mlp(params: Dict[str, Any], device) -> TrialProgram:
@@ -233,12 +253,13 @@ def _mlp(params: Dict[str, Any], device) -> TrialProgram:
     y = (x @ torch.randn(784, 10, generator=g)).argmax(1)
     clip = _clip_grad(params)
     ex = ResidentTrialExecutor(MLP(), (x, y), dev, optimizer="sgd", use_graph=dev.type == "cuda", channels_last=False,
-                               clip_grad=clip, lr_schedule=_lr_schedule(params), loss_hparams=_loss_hparams(params))
-    return _with_loss_hp(_with_schedule(_with_clip(TrialProgram(
+                               clip_grad=clip, lr_schedule=_lr_schedule(params), loss_hparams=_loss_hparams(params),
+                               layerwise=_layerwise(params))
+    return _with_layerwise(_with_loss_hp(_with_schedule(_with_clip(TrialProgram(
         ex, unit_steps=int(params.get("unit_steps", 10)), window=int(params.get("window", 4)),
         hp_keys=("lr", "momentum", "weight_decay"),
         info={"model": "mlp", "batch": bs, "warm_hparams": {"lr": 0.01, "momentum": 0.9},
-              "images_per_step": bs}), clip), params), _loss_hparams(params))
+              "images_per_step": bs}), clip), params), _loss_hparams(params)), _layerwise(params))
 
 
 def _gpt2(params: Dict[str, Any], device, tiny: bool) -> TrialProgram:
@@ -280,8 +301,9 @@ def _gpt2(params: Dict[str, Any], device, tiny: bool) -> TrialProgram:
                                use_graph=bool(params.get("graph", False)), channels_last=False,
                                lp_dtype=torch.bfloat16, clip_grad=clip, lr_schedule=_lr_schedule(params),
                                loss_hparams=loss_hp, dropout=_dropout(params),
-                               dropout_seed=int(params.get("dropout_seed", 0)), attn_dropout=_attn_dropout(params))
-    return _with_attn_dropout(_with_dropout(_with_loss_hp(_with_schedule(_with_clip(TrialProgram(
+                               dropout_seed=int(params.get("dropout_seed", 0)), attn_dropout=_attn_dropout(params),
+                               layerwise=_layerwise(params))
+    return _with_layerwise(_with_attn_dropout(_with_dropout(_with_loss_hp(_with_schedule(_with_clip(TrialProgram(
         ex, unit_steps=int(params.get("unit_steps", 4 if tiny else 10)),
         window=int(params.get("window", 4)),
         hp_keys=("lr", "beta1", "beta2", "eps", "weight_decay"),
@@ -291,7 +313,8 @@ def _gpt2(params: Dict[str, Any], device, tiny: bool) -> TrialProgram:
                                "weight_decay": 0.1},
               "tokens_per_step": batch * seq, "floor_loss": data.floor_loss,
               "unigram_loss": data.unigram_loss, "chance_loss": data.chance_loss,
-              "active_vocab": data.active_vocab}), clip), params), loss_hp), _dropout(params)), _attn_dropout(params))
+              "active_vocab": data.active_vocab}), clip), params), loss_hp), _dropout(params)), _attn_dropout(params)),
+        _layerwise(params))
 
 
 PROGRAMS: Dict[str, Callable[[Dict[str, Any], Any], TrialProgram]] = {

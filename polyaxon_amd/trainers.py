@@ -164,6 +164,9 @@ def train_resnet(argv=None) -> float:
     ap.add_argument("--image", type=int, default=224)
     ap.add_argument("--units", type=int, default=1)
     ap.add_argument("--unit_steps", type=int, default=8)
+    ap.add_argument("--lars", type=float, default=0.0, metavar="TRUST_COEF",
+                    help="LARS: layer-wise trust ratios with this coefficient on every conv / linear weight "
+                         "(csrc/layerwise_kernels.hip); 0 = off: plain SGD, nothing of it is built")
     _schedule_args(ap, warmup=True)
     _loss_args(ap)
     args = _parse(ap, argv)
@@ -178,7 +181,7 @@ def train_resnet(argv=None) -> float:
     sched = args.lr_schedule != "none"
     loss_hp = args.label_smoothing != 0 or args.z_loss != 0
     ex = ResidentTrialExecutor(resnet50(), (x, y), dev, use_graph=False, clip_grad=clip, lr_schedule=sched,
-                               loss_hparams=loss_hp)
+                               loss_hparams=loss_hp, layerwise=args.lars > 0)
     ckpt = _ckpt_path() if args.ckpt else None
     done_units = 0
     ex.reset(seed=args.seed)
@@ -190,9 +193,10 @@ def train_resnet(argv=None) -> float:
         ex.step.fill_(int(st["step"]))
         done_units = int(st["units"])
     # (the executor passes on only what it knows: max_grad_norm exists when clipping is on, the loss's two when the
-    # loss hyper-parameters are)
+    # loss hyper-parameters are, trust_coef under --lars)
     ex.set_hparams(lr=args.lr, momentum=args.momentum, weight_decay=args.weight_decay,
-                   max_grad_norm=args.max_grad_norm, label_smoothing=args.label_smoothing, z_loss=args.z_loss)
+                   max_grad_norm=args.max_grad_norm, label_smoothing=args.label_smoothing, z_loss=args.z_loss,
+                   trust_coef=args.lars)
     if sched:  # the horizon is the trial's full resource: a RESUMEd rung continues the curve at its restored step
         ex.set_hparams(**_schedule_hparams(args, args.units * args.unit_steps))
     ex.run(max(0, args.units - done_units) * args.unit_steps)
@@ -250,6 +254,10 @@ def train_lm(argv=None) -> float:
     ap.add_argument("--attn-dropout", "--attn_dropout", dest="attn_dropout", type=float, default=0.0,
                     help="dropout rate on the attention probabilities (ops/attn_dropout.py: device data, masks redrawn "
                          "inside the flash-attention kernels from the step counter); 0: no state, the plain kernels")
+    ap.add_argument("--lamb", action="store_true",
+                    help="LAMB: AdamW's moments with a layer-wise trust ratio on every matrix "
+                         "(csrc/layerwise_kernels.hip); needs every tensor's whole norm, so not with --zero1 / "
+                         "PLX_OPT_IN_BACKWARD=1")
     _schedule_args(ap, warmup=False)  # --warmup_steps above: host-side without a schedule, the schedule's with one
     _loss_args(ap)
     args = _parse(ap, argv)
@@ -259,6 +267,10 @@ def train_lm(argv=None) -> float:
                  or os.environ.get("PLX_OPT_IN_BACKWARD", "0") == "1"):
         ap.error("--max_grad_norm needs the whole gradient before any update: it cannot be combined with --zero1 / "
                  "PLX_ZERO1=1 / PLX_OPT_IN_BACKWARD=1 (AdamW per bucket inside the backward)")
+    if args.lamb and (args.zero1 or os.environ.get("PLX_ZERO1", "0") == "1"
+                      or os.environ.get("PLX_OPT_IN_BACKWARD", "0") == "1"):
+        ap.error("--lamb needs every weight tensor's whole norm before any update: it cannot be combined with "
+                 "--zero1 / PLX_ZERO1=1 / PLX_OPT_IN_BACKWARD=1 (AdamW per bucket inside the backward)")
     # the process group is the gloo rendezvous; every device collective of the trial (gradient buckets, ZeRO-1,
     # the parameter broadcast, the metric mean) runs on ONE framework RCCL communicator (parallel/comm.py)
     cuda = not args.cpu and torch.cuda.is_available()
@@ -289,7 +301,7 @@ def train_lm(argv=None) -> float:
     step = torch.zeros(1, dtype=torch.int32, device=dev)
     opt = FusedAdamW(flat, lr=args.lr, betas=(0.9, args.beta2), weight_decay=args.weight_decay, step_counter=step,
                      max_grad_norm=args.max_grad_norm if clip else None,
-                     lr_schedule=args.lr_schedule if sched else None)
+                     lr_schedule=args.lr_schedule if sched else None, lamb=args.lamb)
     if sched:  # evaluated on the device every step from `step`: no per-step set_hparams below
         opt.set_hparams(**_schedule_hparams(args, args.steps))
     # PLX_OPT_IN_BACKWARD=1: the AdamW update of each gradient bucket runs inside the backward as the bucket completes
