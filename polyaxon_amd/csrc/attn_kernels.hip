@@ -76,11 +76,38 @@ struct AttnDropArgs {
   uint32_t layer;
 };
 
-template <bool DROP>
-using KArgs = std::conditional_t<DROP, AttnDropArgs, AttnArgs>;
+// ------------------------------------------------------------------------------------------ sliding window
+// Causal self-attention over the last W keys (ops/attn_window.py AttnWindowState): query i sees key j iff
+// i - W < j <= i.  win[0] is W, one int32 of device memory that every kernel loads once at its start (a uniform load:
+// W lives in a scalar register), so one captured step serves every window; W <= 0 is no window.  S == Skv, so every
+// real query keeps its diagonal key: no row is fully masked and lse2 stays finite.  The band changes the loop bounds
+// (the first key tile of a query block, the last query tile of a key block), adds one wave-uniform skip per tile /
+// sub-tile and one term to the element mask of the tiles that straddle a window start; where it removes no key
+// (W <= 0 or W >= S) the kernels visit the plain kernels' tiles in their order and leave their bits.  8 waves only.
+struct AttnWinArgs {
+  AttnArgs a;
+  const int32_t* win;
+};
+
+struct AttnWinDropArgs {
+  AttnDropArgs d;
+  const int32_t* win;
+};
+
+template <bool DROP, bool WIN = false>
+using KArgs = std::conditional_t<WIN, std::conditional_t<DROP, AttnWinDropArgs, AttnWinArgs>,
+                                 std::conditional_t<DROP, AttnDropArgs, AttnArgs>>;
 
 __host__ __device__ __forceinline__ const AttnArgs& attn_args(const AttnArgs& ka) { return ka; }
 __host__ __device__ __forceinline__ const AttnArgs& attn_args(const AttnDropArgs& ka) { return ka.a; }
+__host__ __device__ __forceinline__ const AttnArgs& attn_args(const AttnWinArgs& ka) { return ka.a; }
+__host__ __device__ __forceinline__ const AttnArgs& attn_args(const AttnWinDropArgs& ka) { return ka.d.a; }
+
+// W of this launch, clamped to S: a window of S keys or more removes nothing, and every bound below stays < 2 S + 256
+__device__ __forceinline__ int win_load(const int32_t* win, int S) {
+  const int w = win[0];
+  return w <= 0 || w > S ? S : w;
+}
 
 struct Drop {
   uint32_t T, k0, k1, t, stream;
@@ -91,6 +118,8 @@ __device__ __forceinline__ Drop drop_load(const AttnDropArgs& ka, int bh) {
   return Drop{ka.hp[0], ka.hp[2], ka.hp[3], (uint32_t)ka.step[0], 0x80000000u | (ka.layer << 16) | (uint32_t)bh,
               __uint_as_float(ka.hp[1])};
 }
+
+__device__ __forceinline__ Drop drop_load(const AttnWinDropArgs& ka, int bh) { return drop_load(ka.d, bh); }
 
 // the four words of block (qb, kb) = (q >> 2, k >> 2)
 __device__ __forceinline__ void drop_block(const Drop& d, uint32_t qb, uint32_t kb, uint32_t (&c)[4]) {
@@ -264,6 +293,19 @@ __device__ __forceinline__ void store_row(__bf16* row, const f32x16 (&acc)[D / 3
     }
 }
 
+// WIN, forward and dQ: the key tile of the first key any query of the block (first query q0) sees, staged into the
+// double buffer of its parity so that the tile loop's `j & 1` holds from there.  j0 * 64 <= q0 < S = Skv.
+template <int D, int NW>
+__device__ __forceinline__ int win_first_tile(char* smem, const __bf16* K, const __bf16* V, const AttnArgs& a, int q0,
+                                              int W, int wave, int lane) {
+  constexpr int TB = 64 * 2 * D;
+  const int j0 = max(0, q0 - W + 1) / 64;
+  char* fb = smem + (j0 & 1) * 2 * TB;
+  stage_tile<D, 64, NW>(fb, K + (long long)j0 * 64 * a.sk.s, a.sk.s, a.Skv - j0 * 64, a.zero, wave, lane);
+  stage_tile<D, 64, NW>(fb + TB, V + (long long)j0 * 64 * a.sv.s, a.sv.s, a.Skv - j0 * 64, a.zero, wave, lane);
+  return j0;
+}
+
 struct QBlock {
   int b, hq, hk, q0;
 };
@@ -297,8 +339,15 @@ constexpr float RESCALE_TH = 8.f;
 // ------------------------------------------------------------------------------------------------ forward
 // NW waves x 32 queries per workgroup: one K/V tile in LDS feeds NW * 32 queries (8 waves halve the per-CU LDS-DMA
 // fill of the 4-wave form, which at the MFMA-bound rate needed ~77 GB/s per CU, above what LDS-DMA sustains).
-template <int D, int NW, bool DROP>
-__global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd_kernel(KArgs<DROP> ka) {
+//
+// WIN (the sliding window above): the tile loop starts at the tile of the block's first visible key, staged into the
+// buffer of its parity; a wave skips the tiles that end before its first query's window and masks key <= query - W on
+// the tiles that straddle a window start.  A lane can meet a tile wholly before its own window (its wave's earlier
+// queries need it) ahead of its first visible key: every score is -inf, m_run stays -inf (msub = 0, p = 2^-inf = 0),
+// and the first finite maximum rescales the still-zero o and l by alpha = 0.
+template <int D, int NW, bool DROP, bool WIN = false>
+__global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd_kernel(KArgs<DROP, WIN> ka) {
+  static_assert(!WIN || NW == 8, "the windowed kernels exist in the 8-wave form only");
   constexpr int QB = 32 * NW, TB = 64 * 2 * D, STAGE = 2 * TB, ND = D / 32, NS = D / 16;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const AttnArgs& a = attn_args(ka);
@@ -313,8 +362,14 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd_kernel(KArg
 
   const int kv_end = a.causal ? min(a.Skv, blk.q0 + QB) : a.Skv;
   const int nt = (kv_end + 63) / 64;
-  stage_tile<D, 64, NW>(smem, K, a.sk.s, a.Skv, a.zero, wave, lane);
-  stage_tile<D, 64, NW>(smem + TB, V, a.sv.s, a.Skv, a.zero, wave, lane);
+  int W = 0, j0 = 0;
+  if constexpr (WIN) {
+    W = win_load(ka.win, a.S);
+    j0 = win_first_tile<D, NW>(smem, K, V, a, blk.q0, W, wave, lane);
+  } else {
+    stage_tile<D, 64, NW>(smem, K, a.sk.s, a.Skv, a.zero, wave, lane);
+    stage_tile<D, 64, NW>(smem + TB, V, a.sv.s, a.Skv, a.zero, wave, lane);
+  }
   bf16x8 qf[NS];
   {
     const __bf16* qr = Q + (long long)min(qi, a.S - 1) * a.sq.s + 8 * h;
@@ -328,7 +383,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd_kernel(KArg
   const float c = a.c;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  for (int j = 0; j < nt; ++j) {
+  for (int j = j0; j < nt; ++j) {
     const int kv0 = j * 64;
     if (j + 1 < nt) {
       char* nb = smem + ((j + 1) & 1) * STAGE;
@@ -337,7 +392,8 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd_kernel(KArg
     }
     const char* Ks = smem + (j & 1) * STAGE;
     const char* Vs = Ks + TB;
-    if (!(a.causal && kv0 > q0w + 31)) {  // wave-uniform: tile entirely in this wave's causal future
+    // wave-uniform: tile entirely in this wave's causal future, or (WIN) entirely before its first query's window
+    if (!(a.causal && kv0 > q0w + 31) && !(WIN && kv0 + 63 < q0w - W + 1)) {
       uint32_t keep = 0xffffffffu;
       if constexpr (DROP) {
         if (drop.T != 0) keep = drop_keep_tile(drop, qi, (kv0 >> 2) + h);  // wave-uniform
@@ -348,13 +404,18 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd_kernel(KArg
         st[0] = mfma(row_frag<D>(Ks, ql, 2 * s + h), qf[s], st[0]);
         st[1] = mfma(row_frag<D>(Ks, 32 + ql, 2 * s + h), qf[s], st[1]);
       }
-      if ((a.causal && kv0 + 63 > q0w) || kv0 + 64 > a.Skv) {  // diagonal / ragged tile: mask (raw scores)
+      // diagonal / ragged tile, or (WIN) one that starts before the window of the wave's last query: mask (raw scores)
+      if ((a.causal && kv0 + 63 > q0w) || kv0 + 64 > a.Skv || (WIN && kv0 < q0w + 31 - W + 1)) {
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             const int key = kv0 + 32 * t + acc_row(r, h);
-            if ((a.causal && key > qi) || key >= a.Skv) st[t][r] = NEG_INF;
+            if constexpr (WIN) {  // visible iff qi - W < key <= min(qi, Skv - 1): one unsigned range test
+              if ((unsigned)(key - (qi - W + 1)) >= (unsigned)max(0, min(qi, a.Skv - 1) - qi + W)) st[t][r] = NEG_INF;
+            } else {
+              if ((a.causal && key > qi) || key >= a.Skv) st[t][r] = NEG_INF;
+            }
           }
       }
       float mx = NEG_INF;
@@ -415,8 +476,10 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd_kernel(KArg
 // ------------------------------------------------------------------------------------------- backward: dQ
 // NW waves x 32 queries per workgroup: the K / V tile in LDS serves NW * 32 query rows (see the forward).  Also
 // produces delta[b][h][q] = sum_d dO . O of its rows (read from the stored bf16 O) for itself and the dK/dV kernel.
-template <int D, int NW, bool DROP>
-__global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_bwd_dq_kernel(KArgs<DROP> ka) {
+// WIN: the forward's loop start, skip and element mask (p = 0 at the same elements).
+template <int D, int NW, bool DROP, bool WIN = false>
+__global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_bwd_dq_kernel(KArgs<DROP, WIN> ka) {
+  static_assert(!WIN || NW == 8, "the windowed kernels exist in the 8-wave form only");
   constexpr int QB = 32 * NW, TB = 64 * 2 * D, STAGE = 2 * TB, ND = D / 32, NS = D / 16;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const AttnArgs a = attn_args(ka);  // a copy: the plain instantiation then keeps the instruction stream it had
@@ -429,8 +492,14 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_bwd_dq_kernel(K
   const __bf16* V = a.v + blk.b * a.sv.b + blk.hk * a.sv.h;
   const int kv_end = a.causal ? min(a.Skv, blk.q0 + QB) : a.Skv;
   const int nt = (kv_end + 63) / 64;
-  stage_tile<D, 64, NW>(smem, K, a.sk.s, a.Skv, a.zero, wave, lane);
-  stage_tile<D, 64, NW>(smem + TB, V, a.sv.s, a.Skv, a.zero, wave, lane);
+  int W = 0, j0 = 0;
+  if constexpr (WIN) {
+    W = win_load(ka.win, a.S);
+    j0 = win_first_tile<D, NW>(smem, K, V, a, blk.q0, W, wave, lane);
+  } else {
+    stage_tile<D, 64, NW>(smem, K, a.sk.s, a.Skv, a.zero, wave, lane);
+    stage_tile<D, 64, NW>(smem + TB, V, a.sv.s, a.Skv, a.zero, wave, lane);
+  }
   bf16x8 qf[NS], gf[NS];
   // delta[q] = dO[q] . O[q] is the diagonal of the wave's O . dO^T tile, summed by the same MFMA chain (same k order,
   // same operand slots) as dP^T = V . dO^T below: where a row's softmax is one probability of 1 (O = that V row) the
@@ -464,7 +533,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_bwd_dq_kernel(K
   for (int dt = 0; dt < ND; ++dt) dq[dt] = zero16();
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  for (int j = 0; j < nt; ++j) {
+  for (int j = j0; j < nt; ++j) {
     const int kv0 = j * 64;
     if (j + 1 < nt) {
       char* nb = smem + ((j + 1) & 1) * STAGE;
@@ -473,7 +542,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_bwd_dq_kernel(K
     }
     const char* Ks = smem + (j & 1) * STAGE;
     const char* Vs = Ks + TB;
-    if (!(a.causal && kv0 > q0w + 31)) {
+    if (!(a.causal && kv0 > q0w + 31) && !(WIN && kv0 + 63 < q0w - W + 1)) {
       uint32_t keep = 0xffffffffu;
       if constexpr (DROP) {
         if (drop.T != 0) keep = drop_keep_tile(drop, qi, (kv0 >> 2) + h);  // wave-uniform
@@ -486,7 +555,8 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_bwd_dq_kernel(K
           st[t] = mfma(row_frag<D>(Ks, 32 * t + ql, 2 * s + h), qf[s], st[t]);
           dp[t] = mfma(row_frag<D>(Vs, 32 * t + ql, 2 * s + h), gf[s], dp[t]);
         }
-      const bool mask = (a.causal && kv0 + 63 > q0w) || kv0 + 64 > a.Skv || qi >= a.S;
+      const bool mask = (a.causal && kv0 + 63 > q0w) || kv0 + 64 > a.Skv || qi >= a.S ||
+                        (WIN && kv0 < q0w + 31 - W + 1);
       if constexpr (DROP) {  // dP^T = c M o (V dO^T), before the subtraction of delta
 #pragma unroll
         for (int t = 0; t < 2; ++t)
@@ -500,7 +570,10 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_bwd_dq_kernel(K
           float p = fast_exp2(fmaf(st[t][r], c, -lse2));
           if (mask) {
             const int key = kv0 + 32 * t + acc_row(r, h);
-            if ((a.causal && key > qi) || key >= a.Skv || qi >= a.S) p = 0.f;
+            if constexpr (WIN) {  // the forward's range test; a padded query row (qi >= S) sees nothing
+              const int span = qi < a.S ? min(qi, a.Skv - 1) - qi + W : 0;
+              if ((unsigned)(key - (qi - W + 1)) >= (unsigned)max(0, span)) p = 0.f;
+            } else if ((a.causal && key > qi) || key >= a.Skv || qi >= a.S) p = 0.f;
           }
           st[t][r] = p * (dp[t][r] - dlt);  // dS^T (softmax_scale applied at the end)
         }
@@ -671,8 +744,10 @@ __global__ __launch_bounds__(NT, 1) void attn_bwd_dkdv_kernel(AttnArgs a, float*
 // come straight from global memory into registers (they are fixed for the whole sweep), so LDS holds only the
 // double-buffered { Q tile [64][D] | dO tile [64][D] | lse2[64] | delta[64] } stages; the bf16 dK / dV rows (no GQA)
 // are staged through that region one tensor at a time.
-template <int D, bool DROP>
-__global__ __launch_bounds__(512, 1) void attn_bwd_dkdv8_kernel(KArgs<DROP> ka, float* __restrict__ ws) {
+// WIN: the query sweep ends with the last query that still sees the block's last key; a wave skips the sub-tiles past
+// the last query that sees its last key and masks key <= query - W where a window start crosses its keys.
+template <int D, bool DROP, bool WIN = false>
+__global__ __launch_bounds__(512, 1) void attn_bwd_dkdv8_kernel(KArgs<DROP, WIN> ka, float* __restrict__ ws) {
   constexpr int NW = 8, KBLK = 32 * NW, QTB = 64 * 2 * D, QSTAGE = 2 * QTB + 512, ND = D / 32, NS = D / 16;
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const AttnArgs& a = attn_args(ka);
@@ -692,7 +767,12 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_dkdv8_kernel(KArgs<DROP> ka, 
   const __bf16* Gh = a.dout + b * a.sdo.b + hq * a.sdo.h;
   const long long srow0 = ((long long)b * a.H + hq) * a.S;
   const int qt0 = a.causal ? k0 / 64 : 0;
-  const int total = (a.S + 63) / 64 - qt0;
+  int W = 0, q_end = a.S;
+  if constexpr (WIN) {
+    W = win_load(ka.win, a.S);
+    q_end = min(a.S, k0 + KBLK + W - 1);
+  }
+  const int total = (q_end + 63) / 64 - qt0;
   auto stage_q = [&](int buf, int it) {
     const int q0 = (qt0 + it) * 64;
     char* base = smem + buf * QSTAGE;
@@ -734,6 +814,7 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_dkdv8_kernel(KArgs<DROP> ka, 
     for (int sub = 0; sub < 2; ++sub) {
       const int q0 = (qt0 + it) * 64 + 32 * sub;
       if (a.causal && q0 + 31 < kw0) continue;  // wave-uniform: every query precedes this wave's keys
+      if (WIN && q0 > kw0 + 31 + W - 1) continue;  // wave-uniform: every query's window starts past this wave's keys
       uint32_t keep = 0xffffu;
       if constexpr (DROP) {
         if (drop.T != 0) keep = drop_keep_sub(drop, (q0 >> 2) + h, key);  // wave-uniform
@@ -744,7 +825,8 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_dkdv8_kernel(KArgs<DROP> ka, 
         s_acc = mfma(row_frag<D>(Qs, 32 * sub + kl, 2 * s + h), kf[s], s_acc);  // S[q][key]
         dp = mfma(row_frag<D>(Gs, 32 * sub + kl, 2 * s + h), row_frag<D>(Vimg, 32 * wave + kl, 2 * s + h), dp);
       }
-      const bool mask = (a.causal && kw0 + 31 > q0) || q0 + 32 > a.S || kw0 + 32 > a.Skv;
+      const bool mask = (a.causal && kw0 + 31 > q0) || q0 + 32 > a.S || kw0 + 32 > a.Skv ||
+                        (WIN && q0 + 31 - W + 1 > kw0);
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const float4 l4 = *(const float4*)(st_lse + 32 * sub + 8 * g + 4 * h);
@@ -756,7 +838,9 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_dkdv8_kernel(KArgs<DROP> ka, 
           float p = fast_exp2(fmaf(s_acc[r], c, -lv[e]));
           if (mask) {
             const int q = q0 + 8 * g + 4 * h + e;
-            if ((a.causal && key > q) || q >= a.S || key >= a.Skv) p = 0.f;
+            if constexpr (WIN) {  // visible iff key <= q < min(key + W, S): one unsigned range test
+              if ((unsigned)(q - key) >= (unsigned)(key < a.Skv ? min(W, a.S - key) : 0)) p = 0.f;
+            } else if ((a.causal && key > q) || q >= a.S || key >= a.Skv) p = 0.f;
           }
           if constexpr (DROP) {
             const bool kept = (keep >> r) & 1;
@@ -871,7 +955,25 @@ bool args_ok(const AttnArgs& a, int D) {
   return true;
 }
 
+int bwd_args_check(const AttnArgs& a, int D, const float* ws) {
+  if (!args_ok(a, D)) return 1;
+  const long long strides[] = {a.so.s, a.sdo.s, a.sdq.s, a.sdk.s, a.sdv.s, a.so.h, a.sdo.h, a.sdq.h, a.sdk.h, a.sdv.h};
+  for (long long s : strides)
+    if (s % 8) return 1;
+  if (a.H != a.Hkv && ws == nullptr) return 2;
+  return 0;
+}
+
+// Attention dropout (the contract at the top of this file): the plain entry points' checks, plus hp / step present and
+// the limits of the counter word.  A refused call launches nothing.
+bool drop_ok(const AttnArgs& a, const uint32_t* hp, const int32_t* step, int layer) {
+  if (hp == nullptr || step == nullptr || layer < 0 || layer >= 32768) return false;
+  return (long long)a.B * a.H < 65536;  // b * H + h fits the counter word's low 16 bits
+}
+
 }  // namespace
+
+#ifndef PLX_ATTN_WIN  // libplx_attn: the plain and the dropout entry points
 
 // forward waves per workgroup (A/B knob plx_attn_set_fwd_waves: 4 or 8)
 int g_fwd_waves = 8;
@@ -936,26 +1038,10 @@ int launch_bwd(const KArgs<DROP>& ka, float* ws, hipStream_t stream) {
 PLX_API void plx_attn_set_dq_waves(int nw) { g_dq_waves = nw == 4 ? 4 : 8; }
 PLX_API void plx_attn_set_dkdv_waves(int nw) { g_dkdv_waves = nw == 4 ? 4 : 8; }
 
-static int bwd_args_check(const AttnArgs& a, int D, const float* ws) {
-  if (!args_ok(a, D)) return 1;
-  const long long strides[] = {a.so.s, a.sdo.s, a.sdq.s, a.sdk.s, a.sdv.s, a.so.h, a.sdo.h, a.sdq.h, a.sdk.h, a.sdv.h};
-  for (long long s : strides)
-    if (s % 8) return 1;
-  if (a.H != a.Hkv && ws == nullptr) return 2;
-  return 0;
-}
-
 PLX_API int plx_attn_bwd(const AttnArgs* args, int D, float* ws, hipStream_t stream) {
   const AttnArgs& a = *args;
   if (const int rc = bwd_args_check(a, D, ws)) return rc;
   return D == 128 ? launch_bwd<128>(a, ws, stream) : launch_bwd<64>(a, ws, stream);
-}
-
-// Attention dropout (the contract at the top of this file): the plain entry points' checks, plus hp / step present and
-// the limits of the counter word.  A refused call launches nothing.
-static bool drop_ok(const AttnArgs& a, const uint32_t* hp, const int32_t* step, int layer) {
-  if (hp == nullptr || step == nullptr || layer < 0 || layer >= 32768) return false;
-  return (long long)a.B * a.H < 65536;  // b * H + h fits the counter word's low 16 bits
 }
 
 PLX_API int plx_attn_drop_fwd(const AttnArgs* args, const uint32_t* hp, const int32_t* step, int layer, int D,
@@ -978,3 +1064,74 @@ PLX_API int plx_attn_drop_bwd(const AttnArgs* args, const uint32_t* hp, const in
 }
 
 PLX_API int plx_attn_args_size() { return (int)sizeof(AttnArgs); }
+
+#else  // libplx_attn_win (-DPLX_ATTN_WIN): the sliding-window entry points, a library of its own flags (ops/_native.py)
+
+template <int D, bool DROP>
+int launch_win_fwd(const KArgs<DROP, true>& ka, hipStream_t stream) {
+  constexpr int LDS = 4 * 64 * 2 * D;  // 2 stages x {K, V} x 64 rows
+  static int once = prepare(attn_fwd_kernel<D, 8, DROP, true>, LDS);
+  if (once) return once;
+  const AttnArgs& a = attn_args(ka);
+  const int grid = ((a.S + 255) / 256) * a.H * a.B;
+  hipLaunchKernelGGL((attn_fwd_kernel<D, 8, DROP, true>), dim3(grid), dim3(512), LDS, stream, ka);
+  return (int)hipGetLastError();
+}
+
+template <int D, bool DROP>
+int launch_win_bwd(const KArgs<DROP, true>& ka, float* ws, hipStream_t stream) {
+  constexpr int QLDS = 4 * 64 * 2 * D, KLDS8 = 256 * 2 * D + 2 * (2 * 64 * 2 * D + 512);
+  static_assert(KLDS8 - 256 * 2 * D >= 256 * D * 2, "the dK / dV output staging must fit the stage region");
+  static int once = prepare(attn_bwd_dq_kernel<D, 8, DROP, true>, QLDS) |
+                    prepare(attn_bwd_dkdv8_kernel<D, DROP, true>, KLDS8);
+  if (once) return once;
+  const AttnArgs& a = attn_args(ka);
+  const int grid = ((a.S + 255) / 256) * a.H * a.B;  // S == Skv: query blocks and key blocks alike
+  // the dQ kernel goes first: it writes delta, which the dK/dV kernel reads
+  hipLaunchKernelGGL((attn_bwd_dq_kernel<D, 8, DROP, true>), dim3(grid), dim3(512), QLDS, stream, ka);
+  hipLaunchKernelGGL((attn_bwd_dkdv8_kernel<D, DROP, true>), dim3(grid), dim3(512), KLDS8, stream, ka, ws);
+  if (a.H != a.Hkv) {
+    const long long n8 = (long long)a.B * a.Hkv * a.Skv * (D / 8);
+    const int rgrid = (int)std::min<long long>((n8 + NT - 1) / NT, 2048);
+    hipLaunchKernelGGL(attn_bwd_reduce_kernel<D>, dim3(rgrid), dim3(NT), 0, stream, a, (const float*)ws);
+  }
+  return (int)hipGetLastError();
+}
+
+// The plain entry points' checks, plus: the window word present, causal self-attention (S == Skv).  hp and step are
+// both null (no dropout) or both present (attention dropout inside the band, plx_attn_drop_*'s checks).  A refused call
+// launches nothing.
+static bool win_ok(const AttnArgs& a, const int32_t* win, const uint32_t* hp, const int32_t* step, int layer) {
+  if (win == nullptr || !a.causal || a.S != a.Skv) return false;
+  return (hp == nullptr && step == nullptr) || drop_ok(a, hp, step, layer);
+}
+
+PLX_API int plx_attn_win_fwd(const AttnArgs* args, const int32_t* win, const uint32_t* hp, const int32_t* step,
+                             int layer, int D, hipStream_t stream) {
+  const AttnArgs& a = *args;
+  if (!args_ok(a, D) || !win_ok(a, win, hp, step, layer)) return 1;
+  if (a.so.s % 4 || a.so.h % 4 || a.so.b % 4) return 1;
+  if (hp == nullptr) {
+    const AttnWinArgs ka{a, win};
+    return D == 128 ? launch_win_fwd<128, false>(ka, stream) : launch_win_fwd<64, false>(ka, stream);
+  }
+  const AttnWinDropArgs ka{{a, hp, step, (uint32_t)layer}, win};
+  return D == 128 ? launch_win_fwd<128, true>(ka, stream) : launch_win_fwd<64, true>(ka, stream);
+}
+
+PLX_API int plx_attn_win_bwd(const AttnArgs* args, const int32_t* win, const uint32_t* hp, const int32_t* step,
+                             int layer, int D, float* ws, hipStream_t stream) {
+  const AttnArgs& a = *args;
+  if (const int rc = bwd_args_check(a, D, ws)) return rc;
+  if (!win_ok(a, win, hp, step, layer)) return 1;
+  if (hp == nullptr) {
+    const AttnWinArgs ka{a, win};
+    return D == 128 ? launch_win_bwd<128, false>(ka, ws, stream) : launch_win_bwd<64, false>(ka, ws, stream);
+  }
+  const AttnWinDropArgs ka{{a, hp, step, (uint32_t)layer}, win};
+  return D == 128 ? launch_win_bwd<128, true>(ka, ws, stream) : launch_win_bwd<64, true>(ka, ws, stream);
+}
+
+PLX_API int plx_attn_win_args_size() { return (int)sizeof(AttnArgs); }
+
+#endif

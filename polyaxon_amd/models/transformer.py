@@ -120,6 +120,7 @@ class Attention(nn.Module):
         self.qkv = nn.Linear(cfg.d_model, (cfg.n_heads + 2 * cfg.kv_heads) * hd, bias=cfg.bias)
         self.proj = nn.Linear(cfg.n_heads * hd, cfg.d_model, bias=cfg.bias)
         self._drop = None  # (AttnDropoutState, layer index): Transformer.set_attn_dropout
+        self._window = None  # AttnWindowState: Transformer.set_attn_window
 
     def forward(self, x, rope=None):
         B, S, _ = x.shape
@@ -139,10 +140,14 @@ class Attention(nn.Module):
                 q, k = apply_rope(q, *cs), apply_rope(k, *cs)
         # hand-written CDNA4 flash attention (ops/attention.py, csrc/attn_kernels.hip): GQA straight into the
         # kernel (no repeat_interleave of K/V), output written in [B, S, H, D] so the projection reads it as is
-        if self._drop is not None and self.training:
+        drop = self._drop if self.training else None
+        if self._window is not None:
+            # sliding-window attention (ops/attn_window.py): part of the model, so train and eval alike
+            y = flash_attention(q, k, v, causal=True, drop=drop, window=self._window)
+        elif drop is not None:
             # dropout on the probabilities inside the kernels (ops/attn_dropout.py); an activation-checkpoint
             # recomputation runs at the same step, so it draws the same mask
-            y = flash_attention(q, k, v, causal=True, drop=self._drop)
+            y = flash_attention(q, k, v, causal=True, drop=drop)
         else:
             y = flash_attention(q, k, v, causal=True)
         return lm_ops.linear(y.reshape(B, S, cfg.n_heads * hd), self.proj.weight, self.proj.bias, side=True)
@@ -219,6 +224,12 @@ class Transformer(nn.Module):
         attention call."""
         for l, blk in enumerate(self.blocks):
             blk.attn._drop = None if state is None else (state, l)
+
+    def set_attn_window(self, state) -> None:
+        """Sliding-window attention with the window in device memory (ops/attn_window.py AttnWindowState): every
+        block's attention sees the last W keys, in training and in ``eval()`` alike.  None: the plain attention call."""
+        for blk in self.blocks:
+            blk.attn._window = state
 
     def init_spec(self):
         """(param, kind, scale) for the fused in-place re-initialiser (GPT-2 / Llama conventions)."""

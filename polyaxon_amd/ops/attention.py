@@ -14,6 +14,11 @@ CPU tensors, fp32 and other head dims use the plain fp32 math definition (``_ref
 ``drop=(AttnDropoutState, layer)`` is dropout on the softmax probabilities (ops/attn_dropout.py): the kernels'
 ``plx_attn_drop_*`` entry points read the rate and the step counter from device memory and regenerate the mask in
 the forward and in both backward kernels; nothing is stored.  ``drop=None`` is exactly the plain path.
+
+``window=AttnWindowState`` is sliding-window attention (ops/attn_window.py): query i sees the last W keys, W one
+int32 of device memory that the ``plx_attn_win_*`` entry points (the 8-wave kernels' band variants, a library of
+their own) read at run time; it composes with ``drop``.  Causal self-attention only.  ``window=None`` is exactly
+the calls above.
 """
 from __future__ import annotations
 
@@ -87,17 +92,21 @@ def _reference_mask(drop, B, H, S, Skv, device):
     return torch.from_numpy(m.reshape(B, H, S, Skv)).to(device=device, dtype=torch.float32) * state.c
 
 
-def _reference(q, k, v, causal, scale, drop=None):
+def _reference(q, k, v, causal, scale, drop=None, window=None):
     """Plain fp32 math (matmul + softmax): the CPU path and the path for shapes / dtypes the HIP kernel does not
     take (fp32 reference models, head_dim other than 64 / 128).  No SDPA, so no library attention kernel.  ``drop``:
-    the softmax is multiplied by the twin's scaled mask (ops/attn_dropout.py)."""
+    the softmax is multiplied by the twin's scaled mask (ops/attn_dropout.py).  ``window``: the band of the state's
+    host value (ops/attn_window.py) joins the causal mask."""
     rep = q.shape[1] // k.shape[1]
     kk = k.repeat_interleave(rep, 1) if rep > 1 else k
     vv = v.repeat_interleave(rep, 1) if rep > 1 else v
     s = torch.matmul(q.float(), kk.float().transpose(-1, -2)) * scale
     if causal:
         S, Sk = q.shape[2], k.shape[2]
-        s = s.masked_fill(torch.ones(S, Sk, dtype=torch.bool, device=q.device).triu(1), float("-inf"))
+        hidden = torch.ones(S, Sk, dtype=torch.bool, device=q.device).triu(1)
+        if window is not None and window.W > 0:  # key j <= i - W lies before the window of query i
+            hidden |= torch.ones(S, Sk, dtype=torch.bool, device=q.device).tril(-window.W)
+        s = s.masked_fill(hidden, float("-inf"))
     p = s.softmax(-1)
     if drop is not None:
         p = p * _reference_mask(drop, q.shape[0], q.shape[1], q.shape[2], k.shape[2], q.device)
@@ -119,9 +128,30 @@ def _lib():
     return lib
 
 
+_WIN_CHECKED = False
+
+
+def _win_lib():
+    """The sliding-window library (the same source and argument block as :func:`_lib`'s, built on its own)."""
+    global _WIN_CHECKED
+    lib = _native.lib("plx_attn_win")
+    if not _WIN_CHECKED:
+        _check(lib.plx_attn_win_args_size())
+        _WIN_CHECKED = True
+    return lib
+
+
+def _drop_ptrs(drop):
+    """(hp, step, layer) of the windowed entry points: null pointers without dropout"""
+    if drop is None:
+        return None, None, 0
+    state, layer = drop
+    return state.hp.data_ptr(), state.step_counter.data_ptr(), layer
+
+
 class _FlashAttention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, causal: bool, scale: float, drop=None):
+    def forward(ctx, q, k, v, causal: bool, scale: float, drop=None, window=None):
         lib = _lib()
         q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
         B, H, S, D = q.shape
@@ -130,7 +160,10 @@ class _FlashAttention(torch.autograd.Function):
         a = _args(q, k, v, causal, scale)
         a.out, a.so, a.lse2 = out.data_ptr(), _bhs(out, "bshd"), lse2.data_ptr()
         stream = torch.cuda.current_stream(q.device).cuda_stream
-        if drop is None:
+        if window is not None:
+            rc = _win_lib().plx_attn_win_fwd(ctypes.byref(a), window.win.data_ptr(), *_drop_ptrs(drop), D, stream)
+            _native.check(rc, "plx_attn_win_fwd")
+        elif drop is None:
             _native.check(lib.plx_attn_fwd(ctypes.byref(a), D, stream), "plx_attn_fwd")
         else:
             state, layer = drop
@@ -138,7 +171,7 @@ class _FlashAttention(torch.autograd.Function):
                                        stream)
             _native.check(rc, "plx_attn_drop_fwd")
         ctx.save_for_backward(q, k, v, out, lse2)
-        ctx.causal, ctx.scale, ctx.drop = causal, scale, drop
+        ctx.causal, ctx.scale, ctx.drop, ctx.window = causal, scale, drop, window
         return out
 
     @staticmethod
@@ -160,27 +193,36 @@ class _FlashAttention(torch.autograd.Function):
         ws = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=q.device) if nbytes else None
         wsp = ws.data_ptr() if ws is not None else None
         stream = torch.cuda.current_stream(q.device).cuda_stream
-        if ctx.drop is None:
+        if ctx.window is not None:  # the word the forward read: nothing may set the window in between
+            rc = _win_lib().plx_attn_win_bwd(ctypes.byref(a), ctx.window.win.data_ptr(), *_drop_ptrs(ctx.drop), D, wsp,
+                                             stream)
+            _native.check(rc, "plx_attn_win_bwd")
+        elif ctx.drop is None:
             _native.check(lib.plx_attn_bwd(ctypes.byref(a), D, wsp, stream), "plx_attn_bwd")
         else:  # the same step as the forward: the three kernels redraw its mask
             state, layer = ctx.drop
             rc = lib.plx_attn_drop_bwd(ctypes.byref(a), state.hp.data_ptr(), state.step_counter.data_ptr(), layer, D,
                                        wsp, stream)
             _native.check(rc, "plx_attn_drop_bwd")
-        return dq, dk, dv, None, None, None
+        return dq, dk, dv, None, None, None, None
 
 
 def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = True,
-                    scale: Optional[float] = None, drop=None) -> torch.Tensor:
+                    scale: Optional[float] = None, drop=None, window=None) -> torch.Tensor:
     """softmax(q k^T * scale [+ causal mask]) v with GQA (H % Hkv == 0).  q: [B,H,S,D], k/v: [B,Hkv,Skv,D].
-    Returns [B, S, H, D].  ``drop=(AttnDropoutState, layer)``: dropout on the probabilities (module docstring)."""
+    Returns [B, S, H, D].  ``drop=(AttnDropoutState, layer)``: dropout on the probabilities; ``window=AttnWindowState``:
+    each query sees its last W keys, causal self-attention only (module docstring)."""
     if q.dim() != 4 or k.dim() != 4 or v.shape != k.shape or q.shape[-1] != k.shape[-1]:
         raise ValueError("expected q [B,H,S,D] and k/v [B,Hkv,Skv,D]")
     if q.shape[1] % k.shape[1]:
         raise ValueError("query heads must be a multiple of key/value heads")
+    if window is not None and (not causal or q.shape[2] != k.shape[2]):
+        raise ValueError("window= is causal self-attention only: causal=True and S == Skv")
     scale = 1.0 / math.sqrt(q.shape[-1]) if scale is None else float(scale)
     if not q.is_cuda or q.dtype != torch.bfloat16 or q.shape[-1] not in (64, 128):
-        return _reference(q, k, v, causal, scale, drop)
+        return _reference(q, k, v, causal, scale, drop, window)
+    if window is not None:
+        return _FlashAttention.apply(q, k, v, causal, scale, drop, window)
     if drop is None:
         return _FlashAttention.apply(q, k, v, causal, scale)
     return _FlashAttention.apply(q, k, v, causal, scale, drop)

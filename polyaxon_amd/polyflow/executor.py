@@ -53,7 +53,7 @@ class ResidentTrialExecutor:
                  ring_size: int = 4096, init_spec: Optional[Callable] = None,
                  lp_dtype: Optional[torch.dtype] = None, clip_grad: bool = False, lr_schedule=False,
                  loss_hparams: bool = False, dropout: bool = False, dropout_seed: int = 0,
-                 attn_dropout: bool = False, layerwise: bool = False):
+                 attn_dropout: bool = False, layerwise: bool = False, attn_window: bool = False):
         """``lp_dtype`` (the language models, GPU): the model computes from bf16 weights with bf16 gradients and the
         optimizer keeps the fp32 master (ops/flat.py lp mode); every re-init / restore refreshes the bf16 copy.
         ``clip_grad``: global-norm gradient clipping (ops/optim.py) with ``max_grad_norm`` as one more device
@@ -79,7 +79,12 @@ class ResidentTrialExecutor:
         ``layerwise``: layer-wise trust ratios on every weight tensor of rank 2 or higher (ops/optim.py,
         csrc/layerwise_kernels.hip): ``sgd`` becomes LARS with ``trust_coef`` as one more device hyper-parameter
         (0.001 until a trial sets one), ``adamw`` becomes LAMB.  The DP step is the whole-gradient one, so a gang
-        is fine; the per-bucket optimizer modes are not."""
+        is fine; the per-bucket optimizer modes are not.
+        ``attn_window``: sliding-window attention with the window ``attn_window`` (keys per query) as one more device
+        hyper-parameter (ops/attn_window.py): the model's ``set_attn_window`` gets the state and its attention runs
+        the windowed flash-attention kernels, in training and evaluation alike; 0 -- no window, bitwise the plain
+        step -- until a trial sets one.  Like the other hyper-parameters it does not travel with snapshots: a
+        restored trial runs at the window set last."""
         self.device = torch.device(device)
         self.is_cuda = self.device.type == "cuda"
         if channels_last:
@@ -119,6 +124,15 @@ class ResidentTrialExecutor:
 
             self.attn_dropout = AttnDropoutState(self.device, self.step, seed=dropout_seed)
             model.set_attn_dropout(self.attn_dropout)
+        self.attn_window = None
+        if attn_window:
+            if not hasattr(model, "set_attn_window"):
+                raise ValueError(f"attn_window=True needs a model with set_attn_window(); {type(model).__name__} "
+                                 "has no attention")
+            from polyaxon_amd.ops.attn_window import AttnWindowState
+
+            self.attn_window = AttnWindowState(self.device)
+            model.set_attn_window(self.attn_window)
         # default: cross entropy of the fp32-cast logits; on the GPU in one fused HIP kernel each way (ops/lm.py
         # class_xent: no fp32 logits copy, log-softmax or NLL kernels between the head GEMM and its backward, where the
         # host launching them was the bottleneck of the forward -> backward hand-off; +0.1-0.2 %, r5_class_xent_ab.jsonl)
@@ -375,6 +389,8 @@ class ResidentTrialExecutor:
             self.dropout.set(dropout=hp["dropout"])
         if self.attn_dropout is not None and "attn_dropout" in hp:
             self.attn_dropout.set(attn_dropout=hp["attn_dropout"])
+        if self.attn_window is not None and "attn_window" in hp:
+            self.attn_window.set(attn_window=hp["attn_window"])
         self.opt.set_hparams(**{k: v for k, v in hp.items() if k in self.opt.HP})
 
     def grad_norm(self) -> torch.Tensor:

@@ -39,6 +39,11 @@ trials differ by their weights and rates, not by their masks.  The other program
 (ops/attn_dropout.py, drawn inside the flash-attention kernels) with the rate ``attn_dropout`` as a per-trial
 hyper-parameter, 0 until a trial sets it.  It is independent of ``dropout`` -- either or both may be on -- and shares
 ``dropout_seed``.  The other programs reject it.
+
+``gpt2`` and ``gpt2_tiny`` also take ``params: {attn_window: true}``: sliding-window attention (ops/attn_window.py,
+the windowed flash-attention kernels) with the window ``attn_window`` -- keys per query, counting itself -- as a
+per-trial hyper-parameter, 0 (no window) until a trial sets it.  It composes with ``attn_dropout`` and ``dropout``.
+The other programs reject it.
 """
 from __future__ import annotations
 
@@ -91,6 +96,10 @@ class TrialProgram:
                 from polyaxon_amd.ops import attn_dropout
 
                 ex.set_hparams(**attn_dropout.DEFAULTS)
+            if self.info.get("attn_window"):  # back from the warm-up's window to none
+                from polyaxon_amd.ops import attn_window
+
+                ex.set_hparams(**attn_window.DEFAULTS)
         if ex.is_cuda:
             torch.cuda.synchronize(ex.device)
 
@@ -146,11 +155,30 @@ def _attn_dropout(params: Dict[str, Any]) -> bool:
     return bool(params.get("attn_dropout", False))
 
 
+def _attn_window(params: Dict[str, Any]) -> bool:
+    return bool(params.get("attn_window", False))
+
+
 def _no_dropout(name: str, params: Dict[str, Any]) -> None:
     if _dropout(params) or "dropout_seed" in params:
         raise ValueError(f"program {name} has no dropout sites: `dropout` is a param of gpt2 / gpt2_tiny only")
     if _attn_dropout(params):
         raise ValueError(f"program {name} has no attention: `attn_dropout` is a param of gpt2 / gpt2_tiny only")
+    if _attn_window(params):
+        raise ValueError(f"program {name} has no attention: `attn_window` is a param of gpt2 / gpt2_tiny only")
+
+
+def _with_attn_window(prog: TrialProgram, on: bool) -> TrialProgram:
+    """``attn_window`` programs understand the ``attn_window`` size and warm up at half the sequence, so the warm
+    steps walk the band's skips and masks."""
+    if on:
+        from polyaxon_amd.ops import attn_window
+
+        prog.hp_keys = prog.hp_keys + attn_window.KEYS
+        prog.info["warm_hparams"] = {**prog.info.get("warm_hparams", {}),
+                                     "attn_window": max(1, int(prog.info["seq"]) // 2)}
+        prog.info["attn_window"] = True
+    return prog
 
 
 def _with_attn_dropout(prog: TrialProgram, on: bool) -> TrialProgram:
@@ -302,8 +330,8 @@ def _gpt2(params: Dict[str, Any], device, tiny: bool) -> TrialProgram:
                                lp_dtype=torch.bfloat16, clip_grad=clip, lr_schedule=_lr_schedule(params),
                                loss_hparams=loss_hp, dropout=_dropout(params),
                                dropout_seed=int(params.get("dropout_seed", 0)), attn_dropout=_attn_dropout(params),
-                               layerwise=_layerwise(params))
-    return _with_layerwise(_with_attn_dropout(_with_dropout(_with_loss_hp(_with_schedule(_with_clip(TrialProgram(
+                               layerwise=_layerwise(params), attn_window=_attn_window(params))
+    prog = _with_layerwise(_with_attn_dropout(_with_dropout(_with_loss_hp(_with_schedule(_with_clip(TrialProgram(
         ex, unit_steps=int(params.get("unit_steps", 4 if tiny else 10)),
         window=int(params.get("window", 4)),
         hp_keys=("lr", "beta1", "beta2", "eps", "weight_decay"),
@@ -315,6 +343,7 @@ def _gpt2(params: Dict[str, Any], device, tiny: bool) -> TrialProgram:
               "unigram_loss": data.unigram_loss, "chance_loss": data.chance_loss,
               "active_vocab": data.active_vocab}), clip), params), loss_hp), _dropout(params)), _attn_dropout(params)),
         _layerwise(params))
+    return _with_attn_window(prog, _attn_window(params))
 
 
 PROGRAMS: Dict[str, Callable[[Dict[str, Any], Any], TrialProgram]] = {

@@ -254,6 +254,10 @@ def train_lm(argv=None) -> float:
     ap.add_argument("--attn-dropout", "--attn_dropout", dest="attn_dropout", type=float, default=0.0,
                     help="dropout rate on the attention probabilities (ops/attn_dropout.py: device data, masks redrawn "
                          "inside the flash-attention kernels from the step counter); 0: no state, the plain kernels")
+    ap.add_argument("--attn-window", "--attn_window", dest="attn_window", type=int, default=0,
+                    help="sliding-window attention: every query sees its last N keys (ops/attn_window.py: device data "
+                         "of the windowed flash-attention kernels, training and evaluation alike); 0: no state, the "
+                         "plain kernels")
     ap.add_argument("--lamb", action="store_true",
                     help="LAMB: AdamW's moments with a layer-wise trust ratio on every matrix "
                          "(csrc/layerwise_kernels.hip); needs every tensor's whole norm, so not with --zero1 / "
@@ -333,6 +337,10 @@ def train_lm(argv=None) -> float:
         attn_drop = AttnDropoutState(dev, step, rank=info["rank"])  # `step`: the same rule as above
         attn_drop.set(attn_dropout=args.attn_dropout)
         model.set_attn_dropout(attn_drop)
+    if args.attn_window != 0:  # device data of the windowed attention kernels; 0: not built at all
+        from polyaxon_amd.ops.attn_window import AttnWindowState
+
+        model.set_attn_window(AttnWindowState(dev, args.attn_window))
     metrics = MetricReducer(dev, force_comm=force)  # cross-rank mean of the logged loss (RCCL communicator, GPU)
     g = torch.Generator(device=dev).manual_seed(args.seed + 1000 * info["rank"])
 
