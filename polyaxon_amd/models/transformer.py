@@ -308,6 +308,17 @@ class Transformer(nn.Module):
         return sum(p.numel() for p in self.parameters())
 
 
+def muon_parameter_names(model: "Transformer") -> list:
+    """The hidden weight matrices Muon orthogonalises (``FusedAdamW(muon=)``): the 2-D weights the blocks' attention
+    and MLP modules own.  The token and position embeddings and an untied head are not inside a block and stay on
+    AdamW."""
+    names = []
+    for i, block in enumerate(model.blocks):
+        for part, mod in (("attn", block.attn), ("mlp", block.mlp)):
+            names += [f"blocks.{i}.{part}.{n}" for n, p in mod.named_parameters() if p.dim() == 2]
+    return names
+
+
 def lm_loss(logits: torch.Tensor, tokens: torch.Tensor, loss_hp=None, n_classes: Optional[int] = None) -> torch.Tensor:
     """Next-token cross entropy (targets = tokens shifted left), mean over B * (S - 1) positions: the fused HIP kernels
     on bf16 GPU logits (ops/lm.py next_token_xent), F.cross_entropy in fp32 otherwise.  ``loss_hp`` / ``n_classes``:

@@ -46,6 +46,10 @@ LIBRARIES: Dict[str, dict] = {
     # windowed kernels must equal the plain ones bit for bit.  It costs nothing measurable (profiles/attn_window.md)
     "plx_attn_win": {"sources": ["attn_kernels.hip"], "kind": "hip", "link": [],
                      "flags": ["-DPLX_ATTN_WIN", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]},
+    # Muon's batched Newton-Schulz GEMMs and passes: a library of its own (no other binary changes), built without
+    # packed fp32 arithmetic like the other new libraries
+    "plx_muon": {"sources": ["muon_kernels.hip"], "kind": "hip", "link": [],
+                 "flags": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]},
     "plx_rccl": {"sources": ["rccl_comm.cpp"], "kind": "hip_host", "link": ["-lrccl", "-pthread"]},
 }
 
@@ -250,6 +254,16 @@ SIGNATURES: Dict[str, Dict[str, list]] = {
         "plx_lw_norms": [_I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P],
         "plx_lw_ratios": [_I, _P, _P, _P, _I, _P, _P, _P, _P],
         "plx_lw_update": [_I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P],
+    },
+    "plx_muon": {
+        "plx_muon_chunk": [],
+        "plx_muon_tile": [],
+        "plx_muon_problem_size": [],
+        "plx_muon_prepare": [],
+        "plx_muon_momentum": [_I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P],
+        "plx_muon_norms": [_P, _P, _P, _I, _P, _P],
+        "plx_muon_stage": [_I, _I, _P, _P, _I, _P, _P, _I, _I, _P],
+        "plx_muon_update": [_P, _P, _P, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P],
     },
     "plx_bn": {
         "plx_bn_set_thin": [_I],

@@ -20,6 +20,10 @@ Layer-wise trust ratios (``FusedSGD(trust_coef=)``: LARS; ``FusedAdamW(lamb=True
 well: the per-tensor norms, the ratios and the update are three launches over a chunk table built once
 (csrc/layerwise_kernels.hip), in a fixed summation order, and ``trust_coef`` is one more slot of the tensor.
 
+Muon (``FusedAdamW(muon=<parameter names>)``, opt-in) moves the named weight matrices from AdamW to momentum plus a
+Newton-Schulz orthogonalised update: one batched launch per stage over every such matrix (csrc/muon_kernels.hip,
+ops/muon.py), with ``muon_lr`` and ``muon_momentum`` as two more slots of the tensor.
+
 On CPU (no native library) the same update is computed with torch ops; tests compare the two.
 """
 from __future__ import annotations
@@ -29,7 +33,7 @@ from typing import Dict, Optional
 
 import torch
 
-from polyaxon_amd.ops import _native, lr_schedule as _lrs, side_stream
+from polyaxon_amd.ops import _native, lr_schedule as _lrs, muon as _muon, side_stream
 from polyaxon_amd.ops.flat import FlatParams
 
 
@@ -246,6 +250,7 @@ class _Layerwise:
     (``step_range_``, ``FlatDDP(optimizer=...)``, ZeRO-1) cannot see a whole norm and are refused."""
 
     _lw: Optional[_LayerNorms] = None
+    _mu = None  # FusedAdamW(muon=): the Muon segments and their plan
     _in_backward = False
 
     def _init_layerwise(self, flat: FlatParams, mode: Optional[int], key: Optional[str] = None) -> None:
@@ -265,6 +270,9 @@ class _Layerwise:
         if self._lw is not None:
             raise ValueError(f"a layer-wise optimizer (LARS / LAMB) needs every segment's whole norm before any "
                              f"update: it has no {what} (step_range_, FlatDDP(optimizer=...), ZeRO-1)")
+        if self._mu is not None:
+            raise ValueError(f"Muon orthogonalises every selected matrix's whole update: it has no {what} "
+                             f"(step_range_, FlatDDP(optimizer=...), ZeRO-1)")
 
     # set by FlatDDP(optimizer=...): the update runs per gradient bucket during the backward (step_range_), and
     # step_() only closes the step's bookkeeping
@@ -277,6 +285,41 @@ class _Layerwise:
         if on:
             self._no_ranges("per-bucket update inside the backward")
         self._in_backward = bool(on)
+
+
+class _MuonSegments:
+    """The host side of ``FusedAdamW(muon=)``: the named segments (rank-2 decay segments, both dimensions multiples of
+    8, so every vector access of the kernels is whole), the contiguous runs of every other flat element, which keep
+    AdamW (in lp mode cut at the bf16 / fp32 boundary), and on the GPU the plan of ops/muon.py."""
+
+    LR, MOMENTUM = 6, 7  # hp slots
+
+    def __init__(self, flat: FlatParams, names):
+        by_name = {s.name: s for s in flat.segments}
+        self.segs = []
+        for name in names:
+            seg = by_name.get(name)
+            if seg is None:
+                raise ValueError(f"muon: no parameter named {name!r}")
+            if not seg.decay or len(seg.shape) != 2 or seg.shape[0] % 8 or seg.shape[1] % 8:
+                raise ValueError(f"muon: {name!r} {tuple(seg.shape)} is no weight matrix with both dimensions "
+                                 f"multiples of 8")
+            self.segs.append(seg)
+        self.segs.sort(key=lambda s: s.offset)
+        cuts = [flat.n_decay] if flat.lp_params is not None else []
+        self.runs, at = [], 0
+        for lo, hi in [(s.offset, s.offset + s.numel) for s in self.segs] + [(flat.numel, flat.numel)]:
+            for edge in cuts + [lo]:
+                if at < edge <= lo:
+                    self.runs.append((at, edge))
+                    at = edge
+            at = hi
+        self.plan = None
+        if flat.params.is_cuda:
+            self.plan = _muon.MuonPlan([s.shape for s in self.segs], [s.offset for s in self.segs], flat.device)
+
+    def spans(self):
+        return [(s.offset, s.offset + s.numel, s.shape) for s in self.segs]
 
 
 def lr_factor(kind, s, W, T, m, gamma, E) -> torch.Tensor:
@@ -509,8 +552,14 @@ class FusedAdamW(_Clipping, _Layerwise, _Scheduled):
 
     def __init__(self, flat: FlatParams, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 1e-2, step_counter: Optional[torch.Tensor] = None,
-                 max_grad_norm: Optional[float] = None, lr_schedule: Optional[str] = None, lamb: bool = False):
-        """``lamb``: LAMB on the decay segments for the optimizer's lifetime (fp32 and lp mode; no hyper-parameter
+                 max_grad_norm: Optional[float] = None, lr_schedule: Optional[str] = None, lamb: bool = False,
+                 muon=None, muon_lr: float = 0.02, muon_momentum: float = 0.95):
+        """``muon``: names of weight matrices that get Muon instead of AdamW for the optimizer's lifetime:
+        m <- mu m + g, u = g + mu m (Nesterov), O = five Newton-Schulz iterations on u / (|u| + 1e-7),
+        w <- w (1 - lr_m wd) - lr_m sqrt(max(1, rows / cols)) O, with lr_m = ``muon_lr`` x the LR schedule's factor.
+        The momentum lives in ``exp_avg``; ``muon_lr`` / ``muon_momentum`` are device hyper-parameters (hp slots
+        6, 7).  Every other element keeps AdamW.  Not with ``lamb`` or the per-bucket updates.  None: nothing exists.
+        ``lamb``: LAMB on the decay segments for the optimizer's lifetime (fp32 and lp mode; no hyper-parameter
         of its own); it excludes the per-bucket updates like clipping does.
         ``max_grad_norm``: a number enables global-norm gradient clipping for the optimizer's lifetime (a device
         hyper-parameter like the others; 0 = measure the norm, no limit); None: no clipping at all.  Clipping needs
@@ -528,9 +577,18 @@ class FusedAdamW(_Clipping, _Layerwise, _Scheduled):
         self._init_clip(flat, max_grad_norm)
         if lamb:
             self._init_layerwise(flat, _LayerNorms.LAMB if flat.lp_params is None else _LayerNorms.LAMB_LP)
+        mu = {}
+        if muon is not None:
+            if lamb:
+                raise ValueError("muon= and lamb=True both claim the weight matrices' update: choose one")
+            self._mu = _MuonSegments(flat, muon)
+            if len(self.HP) == _GradClip.SLOT:
+                self.HP = self.HP + ("_slot5",)  # no clipping: slot 5 stays 0, as under _init_layerwise
+            self.HP = self.HP + ("muon_lr", "muon_momentum")  # this instance only: hp slots 6 and 7
+            mu = {"muon_lr": muon_lr, "muon_momentum": muon_momentum}
         sched = self._init_sched(flat, lr_schedule)
         self.set_hparams(lr=lr, beta1=betas[0], beta2=betas[1], eps=eps, weight_decay=weight_decay,
-                         **({"max_grad_norm": max_grad_norm} if self.clipping else {}), **sched)
+                         **({"max_grad_norm": max_grad_norm} if self.clipping else {}), **mu, **sched)
 
     def set_hparams(self, **hp) -> None:
         self._set_hparams("AdamW", hp)
@@ -570,6 +628,9 @@ class FusedAdamW(_Clipping, _Layerwise, _Scheduled):
         st = _stream_ptr(f.params)
         if self._lw is not None:
             self._step_layerwise(lib, st)
+            return
+        if self._mu is not None:
+            self._step_muon(lib, st)
             return
         if self._clip is not None:
             self._step_clipped(lib, st)
@@ -632,6 +693,28 @@ class FusedAdamW(_Clipping, _Layerwise, _Scheduled):
             else:
                 _native.check(lib.plx_adamw_flat(*args, st), "plx_adamw_flat")
 
+    def _step_muon(self, lib, st: int) -> None:
+        """[Norm pass + finalize of the clip,] Muon over its matrices (ops/muon.py MuonPlan.step) and the AdamW
+        launches, plain or clipped, over the runs between them, all on the current stream."""
+        f, clip = self.flat, self._clip
+        side_stream.join(f.device)  # the momentum pass reads gradient slots the side-stream GEMMs write
+        if clip is not None:
+            clip.measure(self.hp, st)
+        state = clip.state if clip is not None else None
+        self._mu.plan.step(f, self.exp_avg, self.hp, self._sched.sched if self._sched is not None else None, state, st)
+        hp, step, nd = self.hp.data_ptr(), self.step.data_ptr(), f.n_decay
+        tail = (state.data_ptr(), st) if clip is not None else (st,)
+        for lo, hi in self._mu.runs:
+            p, m, v = (t.data_ptr() + 4 * lo for t in (f.params, self.exp_avg, self.exp_avg_sq))
+            if f.lp_params is not None and hi <= nd:
+                fn = lib.plx_adamw_mixed_clip if clip is not None else lib.plx_adamw_mixed
+                _native.check(fn(p, f.lp_grads.data_ptr() + 2 * lo, m, v, f.lp_params.data_ptr() + 2 * lo, hi - lo, 1,
+                                 hp, step, *tail), "plx_adamw_mixed")
+            else:
+                fn = lib.plx_adamw_flat_clip if clip is not None else lib.plx_adamw_flat
+                _native.check(fn(p, f.grads.data_ptr() + 4 * (lo - f.grad_base), m, v, hi - lo,
+                                 max(0, min(hi, nd) - lo), hp, step, *tail), "plx_adamw_flat")
+
     def step_range_(self, lo: int, hi: int, stream: Optional[int] = None, state_off: Optional[int] = None) -> None:
         """AdamW over flat elements [lo, hi) on ``stream`` (a FlatDDP bucket: 4-aligned, and in lp mode entirely
         inside the bf16 decay segment or entirely inside the fp32 tail).  The same per-element update as
@@ -685,6 +768,9 @@ class FusedAdamW(_Clipping, _Layerwise, _Scheduled):
                 f.zero_grads()
                 return
             g = g * scale  # a rounding step of its own, before the moments
+        if self._mu is not None:  # the Muon matrices sit AdamW's update out: their state is put back below
+            held = [(lo, hi, shape, f.params[lo:hi].clone(), self.exp_avg[lo:hi].clone(), g[lo:hi].clone())
+                    for lo, hi, shape in self._mu.spans()]
         nd = f.n_decay if self._lw is None else 0  # LAMB: the decay term is part of u
         f.params[:nd].mul_(1.0 - lr * wd)
         self.exp_avg.mul_(b1).add_(g, alpha=1 - b1)
@@ -702,6 +788,16 @@ class FusedAdamW(_Clipping, _Layerwise, _Scheduled):
                 r = wn / un if float(wn) > 0.0 and float(un) > 0.0 else 1.0
                 w.sub_(lr * r * us)
             f.params[f.n_decay:].sub_(lr * u[f.n_decay:])
+        if self._mu is not None:
+            lr_m, mu = self.hp[_MuonSegments.LR], self.hp[_MuonSegments.MOMENTUM]
+            if self._sched is not None and float(self._sched.sched[0]) > 0.0:
+                lr_m = lr_m * (self.hp[0] / self._sched.sched[0])
+            for lo, hi, shape, w, m, gm in held:
+                m.mul_(mu).add_(gm)
+                o = _muon.newton_schulz_reference((gm + mu * m).view(shape)).reshape(-1).float()
+                self.exp_avg[lo:hi] = m
+                self.exp_avg_sq[lo:hi] = 0.0
+                f.params[lo:hi] = w * (1.0 - lr_m * wd) - lr_m * max(1.0, shape[0] / shape[1]) ** 0.5 * o
         f.zero_grads()
         f.sync_lp()
 

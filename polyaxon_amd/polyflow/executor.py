@@ -53,7 +53,8 @@ class ResidentTrialExecutor:
                  ring_size: int = 4096, init_spec: Optional[Callable] = None,
                  lp_dtype: Optional[torch.dtype] = None, clip_grad: bool = False, lr_schedule=False,
                  loss_hparams: bool = False, dropout: bool = False, dropout_seed: int = 0,
-                 attn_dropout: bool = False, layerwise: bool = False, attn_window: bool = False):
+                 attn_dropout: bool = False, layerwise: bool = False, attn_window: bool = False,
+                 muon=None):
         """``lp_dtype`` (the language models, GPU): the model computes from bf16 weights with bf16 gradients and the
         optimizer keeps the fp32 master (ops/flat.py lp mode); every re-init / restore refreshes the bf16 copy.
         ``clip_grad``: global-norm gradient clipping (ops/optim.py) with ``max_grad_norm`` as one more device
@@ -84,7 +85,9 @@ class ResidentTrialExecutor:
         hyper-parameter (ops/attn_window.py): the model's ``set_attn_window`` gets the state and its attention runs
         the windowed flash-attention kernels, in training and evaluation alike; 0 -- no window, bitwise the plain
         step -- until a trial sets one.  Like the other hyper-parameters it does not travel with snapshots: a
-        restored trial runs at the window set last."""
+        restored trial runs at the window set last.
+        ``muon`` (``adamw``): names of the weight matrices that get Muon (ops/optim.py, csrc/muon_kernels.hip), with
+        ``muon_lr`` and ``muon_momentum`` as two more device hyper-parameters; not together with ``layerwise``."""
         self.device = torch.device(device)
         self.is_cuda = self.device.type == "cuda"
         if channels_last:
@@ -101,10 +104,14 @@ class ResidentTrialExecutor:
             self.opt = FusedSGD(self.flat, step_counter=self.step, max_grad_norm=clip, lr_schedule=sched,
                                 trust_coef=0.001 if layerwise else None)
         elif optimizer == "adamw":
+            if muon is not None and layerwise:
+                raise ValueError("muon and layerwise (LAMB) both claim the weight matrices' update: choose one")
             self.opt = FusedAdamW(self.flat, step_counter=self.step, max_grad_norm=clip, lr_schedule=sched,
-                                  lamb=bool(layerwise))
+                                  lamb=bool(layerwise), muon=muon)
         else:
             raise ValueError(f"unknown optimizer {optimizer!r}")
+        if muon is not None and optimizer != "adamw":
+            raise ValueError("muon needs optimizer='adamw'")
         # off: nothing exists -- no tensor, the plain launches, and set_hparams drops the key
         self.dropout = None
         if dropout:

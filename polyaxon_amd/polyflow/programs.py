@@ -44,6 +44,11 @@ hyper-parameter, 0 until a trial sets it.  It is independent of ``dropout`` -- e
 the windowed flash-attention kernels) with the window ``attn_window`` -- keys per query, counting itself -- as a
 per-trial hyper-parameter, 0 (no window) until a trial sets it.  It composes with ``attn_dropout`` and ``dropout``.
 The other programs reject it.
+
+``gpt2`` and ``gpt2_tiny`` also take ``params: {muon: true}``: Muon on the blocks' attention and MLP weight matrices
+(ops/optim.py, csrc/muon_kernels.hip; the embeddings and everything 1-D stay on AdamW) with ``muon_lr`` and
+``muon_momentum`` as per-trial hyper-parameters, 0.02 and 0.95 until a trial sets them.  Not together with
+``layerwise``.  The other programs reject it.
 """
 from __future__ import annotations
 
@@ -131,6 +136,19 @@ def _with_layerwise(prog: TrialProgram, on: bool) -> TrialProgram:
     return prog
 
 
+def _muon(params: Dict[str, Any]) -> bool:
+    return bool(params.get("muon", False))
+
+
+def _with_muon(prog: TrialProgram, on: bool) -> TrialProgram:
+    """``muon`` programs understand ``muon_lr`` and ``muon_momentum``."""
+    if on:
+        prog.hp_keys = prog.hp_keys + ("muon_lr", "muon_momentum")
+        prog.info["warm_hparams"] = {**prog.info.get("warm_hparams", {}), "muon_lr": 0.02, "muon_momentum": 0.95}
+        prog.info["muon"] = True
+    return prog
+
+
 def _loss_hparams(params: Dict[str, Any]) -> bool:
     return bool(params.get("loss_hparams", False))
 
@@ -166,6 +184,8 @@ def _no_dropout(name: str, params: Dict[str, Any]) -> None:
         raise ValueError(f"program {name} has no attention: `attn_dropout` is a param of gpt2 / gpt2_tiny only")
     if _attn_window(params):
         raise ValueError(f"program {name} has no attention: `attn_window` is a param of gpt2 / gpt2_tiny only")
+    if _muon(params):
+        raise ValueError(f"program {name} has no transformer blocks: `muon` is a param of gpt2 / gpt2_tiny only")
 
 
 def _with_attn_window(prog: TrialProgram, on: bool) -> TrialProgram:
@@ -296,7 +316,7 @@ def _gpt2(params: Dict[str, Any], device, tiny: bool) -> TrialProgram:
     """GPT-2 125M (BASELINE.json config 4's trial) on the synthetic copy-task token stream (ops/synth.py
     SyntheticTokens): bf16 weights / gradients with an fp32 master and fused AdamW (the LM trainer's numerics),
     every trial re-initialised in place (GPT-2 init via plx_init_flat), AdamW hyper-parameters as device data."""
-    from polyaxon_amd.models.transformer import Transformer, gpt2_125m, lm_loss
+    from polyaxon_amd.models.transformer import Transformer, gpt2_125m, lm_loss, muon_parameter_names
     from polyaxon_amd.ops.synth import SyntheticChain, SyntheticTokens
     from polyaxon_amd.polyflow.executor import ResidentTrialExecutor
 
@@ -330,7 +350,8 @@ def _gpt2(params: Dict[str, Any], device, tiny: bool) -> TrialProgram:
                                lp_dtype=torch.bfloat16, clip_grad=clip, lr_schedule=_lr_schedule(params),
                                loss_hparams=loss_hp, dropout=_dropout(params),
                                dropout_seed=int(params.get("dropout_seed", 0)), attn_dropout=_attn_dropout(params),
-                               layerwise=_layerwise(params), attn_window=_attn_window(params))
+                               layerwise=_layerwise(params), attn_window=_attn_window(params),
+                               muon=muon_parameter_names(model) if _muon(params) else None)
     prog = _with_layerwise(_with_attn_dropout(_with_dropout(_with_loss_hp(_with_schedule(_with_clip(TrialProgram(
         ex, unit_steps=int(params.get("unit_steps", 4 if tiny else 10)),
         window=int(params.get("window", 4)),
@@ -343,7 +364,7 @@ def _gpt2(params: Dict[str, Any], device, tiny: bool) -> TrialProgram:
               "unigram_loss": data.unigram_loss, "chance_loss": data.chance_loss,
               "active_vocab": data.active_vocab}), clip), params), loss_hp), _dropout(params)), _attn_dropout(params)),
         _layerwise(params))
-    return _with_attn_window(prog, _attn_window(params))
+    return _with_muon(_with_attn_window(prog, _attn_window(params)), _muon(params))
 
 
 PROGRAMS: Dict[str, Callable[[Dict[str, Any], Any], TrialProgram]] = {

@@ -219,7 +219,8 @@ def train_resnet(argv=None) -> float:
 
 # ------------------------------------------------------------------ configs 4 & 5: language models, DP over RCCL
 def train_lm(argv=None) -> float:
-    from polyaxon_amd.models.transformer import Transformer, gpt2_125m, llama3_8b, lm_loss, tiny_llama
+    from polyaxon_amd.models.transformer import (Transformer, gpt2_125m, llama3_8b, lm_loss, muon_parameter_names,
+                                                  tiny_llama)
     from polyaxon_amd.ops.flat import FlatParams
     from polyaxon_amd.ops.optim import FusedAdamW
     from polyaxon_amd.parallel.ddp import FlatDDP, MetricReducer, init_from_env
@@ -262,6 +263,12 @@ def train_lm(argv=None) -> float:
                     help="LAMB: AdamW's moments with a layer-wise trust ratio on every matrix "
                          "(csrc/layerwise_kernels.hip); needs every tensor's whole norm, so not with --zero1 / "
                          "PLX_OPT_IN_BACKWARD=1")
+    ap.add_argument("--muon", action="store_true",
+                    help="Muon on the blocks' attention and MLP weight matrices: momentum, then five Newton-Schulz "
+                         "iterations batched over every matrix (csrc/muon_kernels.hip); everything else keeps AdamW; "
+                         "needs every matrix's whole update, so not with --lamb / --zero1 / PLX_OPT_IN_BACKWARD=1")
+    ap.add_argument("--muon-lr", "--muon_lr", dest="muon_lr", type=float, default=0.02)
+    ap.add_argument("--muon-momentum", "--muon_momentum", dest="muon_momentum", type=float, default=0.95)
     _schedule_args(ap, warmup=False)  # --warmup_steps above: host-side without a schedule, the schedule's with one
     _loss_args(ap)
     args = _parse(ap, argv)
@@ -275,6 +282,10 @@ def train_lm(argv=None) -> float:
                       or os.environ.get("PLX_OPT_IN_BACKWARD", "0") == "1"):
         ap.error("--lamb needs every weight tensor's whole norm before any update: it cannot be combined with "
                  "--zero1 / PLX_ZERO1=1 / PLX_OPT_IN_BACKWARD=1 (AdamW per bucket inside the backward)")
+    if args.muon and (args.lamb or args.zero1 or os.environ.get("PLX_ZERO1", "0") == "1"
+                      or os.environ.get("PLX_OPT_IN_BACKWARD", "0") == "1"):
+        ap.error("--muon needs every weight matrix's whole update before any step: it cannot be combined with "
+                 "--lamb / --zero1 / PLX_ZERO1=1 / PLX_OPT_IN_BACKWARD=1 (AdamW per bucket inside the backward)")
     # the process group is the gloo rendezvous; every device collective of the trial (gradient buckets, ZeRO-1,
     # the parameter broadcast, the metric mean) runs on ONE framework RCCL communicator (parallel/comm.py)
     cuda = not args.cpu and torch.cuda.is_available()
@@ -305,7 +316,9 @@ def train_lm(argv=None) -> float:
     step = torch.zeros(1, dtype=torch.int32, device=dev)
     opt = FusedAdamW(flat, lr=args.lr, betas=(0.9, args.beta2), weight_decay=args.weight_decay, step_counter=step,
                      max_grad_norm=args.max_grad_norm if clip else None,
-                     lr_schedule=args.lr_schedule if sched else None, lamb=args.lamb)
+                     lr_schedule=args.lr_schedule if sched else None, lamb=args.lamb,
+                     muon=muon_parameter_names(model) if args.muon else None, muon_lr=args.muon_lr,
+                     muon_momentum=args.muon_momentum)
     if sched:  # evaluated on the device every step from `step`: no per-step set_hparams below
         opt.set_hparams(**_schedule_hparams(args, args.steps))
     # PLX_OPT_IN_BACKWARD=1: the AdamW update of each gradient bucket runs inside the backward as the bucket completes
