@@ -26,6 +26,16 @@ all-hipBLASLt on one box).  ``SCHEDULE`` holds the shapes that go to the kernel 
 shape goes to the kernel when it is a split-K shape (``plx_gemm256_splits > 1``: the narrow-output, long-reduction
 weight gradients) and to hipBLASLt otherwise.  The choice is a pure function of the shape -- reproducible, and the
 same kernel on every DP rank.  :func:`decisions` lists the shapes seen and what ran.
+
+Edge shapes (``PLX_LM_GEMM_EDGE``, default ``0``): csrc/gemm_edge.hip is the same contract on a bounds-checked
+128x128x64 tile for every M, N, K that are multiples of 8 (:func:`edge_supported`): token counts such as 12 x 1000,
+``d_model`` 1600 or 896, the tiny configs, a 1000-class head.  :func:`gemm` always runs it for a shape that is
+``edge_supported`` but not ``supported`` (no GELU epilogues there).  With ``PLX_LM_GEMM_EDGE=1`` (and ``PLX_LM_GEMM``
+not ``0``) the dispatch -- :func:`matmul`, :func:`forward`, :func:`dgrad`, :func:`wgrad`, :func:`linear_supported`
+-- sends those shapes to it too and :func:`decisions` reports them with schedule ``EDGE``; at the default they go to
+hipBLASLt as before and the library is never loaded.  First numbers (profiles/gemm_edge.md): split-K weight gradients
+and small problems ahead of hipBLASLt (1.07-2.4x), large forwards and data gradients behind (down to 0.60x), and
+behind gemm256 on most 256-multiples -- ``auto`` does not route to it until a per-class rule is made from them.
 """
 from __future__ import annotations
 
@@ -71,6 +81,7 @@ SCHEDULE: Dict[Tuple[int, int, int, bool, bool], int] = {
 # A/B override of the schedule for every kernel call (scripts/gemm_bench.py --waves); 0 = the table
 FORCE_SCHEDULE = 0
 SK = 9  # the persistent stream-K schedule (no accumulate: such calls run the 8-wave kernel)
+EDGE = 128  # decisions(): the edge-tile kernel (csrc/gemm_edge.hip), named after its tile
 
 # schedule of a kernel call outside the table, by layout (PLX_LM_GEMM=1, split-K shapes): the persistent stream-K
 # kernel for the forward (both operands K-major: 2.85 vs 3.10 ms over one call of each of the 9 forward shapes in
@@ -99,6 +110,29 @@ def mode() -> str:
 def enabled() -> bool:
     """PLX_LM_GEMM=0 routes the LM linears back to hipBLASLt (A/B knob)."""
     return mode() != "0"
+
+
+def edge_enabled() -> bool:
+    """PLX_LM_GEMM_EDGE=1 (and PLX_LM_GEMM != 0): the dispatch sends the shapes only the edge-tile kernel takes to
+    it instead of hipBLASLt."""
+    return os.environ.get("PLX_LM_GEMM_EDGE", "0") == "1" and enabled()
+
+
+def edge_supported(M: int, N: int, K: int) -> bool:
+    """csrc/gemm_edge.hip: every dimension a positive multiple of 8 (16-byte chunks never straddle a matrix edge)"""
+    return M > 0 and N > 0 and K > 0 and M % 8 == 0 and N % 8 == 0 and K % 8 == 0
+
+
+def _edge_only(M: int, N: int, K: int) -> bool:
+    return edge_supported(M, N, K) and not supported(M, N, K)
+
+
+def _use_edge(M, N, K, a_kmajor, b_kmajor) -> bool:
+    """Does the dispatch run this shape on the edge-tile kernel?  (Recorded for :func:`decisions`.)"""
+    if not (edge_enabled() and _edge_only(M, N, K)):
+        return False
+    _seen[(M, N, K, bool(a_kmajor), bool(b_kmajor))] = EDGE
+    return True
 
 
 def splits(M: int, N: int, K: int) -> int:
@@ -147,7 +181,8 @@ def _torch_gemm(a, b, M, N, K, a_kmajor, b_kmajor, out=None, accumulate=False, a
 
 def matmul(a, b, M, N, K, a_kmajor, b_kmajor, out=None, accumulate=False) -> torch.Tensor:
     """:func:`gemm` semantics on whichever of the MFMA kernel / hipBLASLt the dispatch picks."""
-    if a.is_cuda and supported(M, N, K) and _use_native(M, N, K, a_kmajor, b_kmajor):
+    if a.is_cuda and ((supported(M, N, K) and _use_native(M, N, K, a_kmajor, b_kmajor))
+                      or _use_edge(M, N, K, a_kmajor, b_kmajor)):
         return gemm(a, b, M, N, K, a_kmajor, b_kmajor, out=out, accumulate=accumulate)
     return _torch_gemm(a, b, M, N, K, a_kmajor, b_kmajor, out=out, accumulate=accumulate)
 
@@ -177,8 +212,11 @@ def gemm(a: torch.Tensor, b: torch.Tensor, M: int, N: int, K: int, a_kmajor: boo
     ``gelu_h``: a bf16 tensor laid out like ``out``; the epilogue stores bf16(A.B) * gelu_tanh'(gelu_h) instead (an
     MLP's GELU backward fused into the down-projection's data gradient; the stream-K schedule only, see
     :func:`gelu_bwd_supported`)."""
-    if not supported(M, N, K):
-        raise ValueError(f"gemm256 needs M, N % 256 == 0 and K % 64 == 0 (got {M}x{N}x{K})")
+    edge = not supported(M, N, K)
+    if edge and not edge_supported(M, N, K):
+        raise ValueError(f"the GEMM kernels need M, N, K > 0 and multiples of 8 (got {M}x{N}x{K})")
+    if edge and (gelu_out is not None or gelu_h is not None):
+        raise ValueError(f"the GELU epilogues need M, N % 256 == 0 and K % 64 == 0 (got {M}x{N}x{K})")
     if a.dtype != torch.bfloat16 or b.dtype != torch.bfloat16 or not (a.is_contiguous() and b.is_contiguous()):
         raise ValueError("gemm256 takes contiguous bf16 operands")
     if a.numel() != M * K or b.numel() != N * K:
@@ -198,6 +236,8 @@ def gemm(a: torch.Tensor, b: torch.Tensor, M: int, N: int, K: int, a_kmajor: boo
     if gelu_out is not None and (accumulate or gelu_out.dtype != torch.bfloat16 or gelu_out.shape != out.shape
                                  or gelu_out.stride() != out.stride() or gelu_out.data_ptr() % 16):
         raise ValueError("gelu_out must be a bf16 tensor laid out like out (and no accumulate)")
+    if edge:
+        return _gemm_edge(a, b, out, M, N, K, a_kmajor, b_kmajor, alpha, accumulate, bias)
     lib = _native.lib("plx_gemm")
     v = _schedule_of(M, N, K, a_kmajor, b_kmajor)
     if gelu_h is not None:
@@ -220,6 +260,21 @@ def gemm(a: torch.Tensor, b: torch.Tensor, M: int, N: int, K: int, a_kmajor: boo
                              gelu_out.data_ptr() if gelu_out is not None else None, v, _native.current_stream())
     if rc != 0:
         raise RuntimeError(f"plx_gemm256 failed ({rc}) for {M}x{N}x{K} a_kmajor={a_kmajor} b_kmajor={b_kmajor}")
+    return out
+
+
+def _gemm_edge(a, b, out, M, N, K, a_kmajor, b_kmajor, alpha, accumulate, bias):
+    """the bounds-checked 128x128x64 kernel (csrc/gemm_edge.hip); arguments already checked by :func:`gemm`"""
+    if out.stride(0) % 8 or out.data_ptr() % 16:
+        raise ValueError("out needs a row stride that is a multiple of 8 and a 16-byte aligned start")
+    floats = _native.size("plx_gemm_edge", "plx_gemm_edge_ws", M, N, K)
+    ws = _workspace(a.device, floats).data_ptr() if floats else None
+    rc = _native.lib("plx_gemm_edge").plx_gemm_edge(
+        a.data_ptr(), b.data_ptr(), out.data_ptr(), ws, M, N, K, K if a_kmajor else M, K if b_kmajor else N,
+        out.stride(0), int(a_kmajor), int(b_kmajor), float(alpha), int(accumulate),
+        bias.data_ptr() if bias is not None else None, _native.current_stream())
+    if rc != 0:
+        raise RuntimeError(f"plx_gemm_edge failed ({rc}) for {M}x{N}x{K} a_kmajor={a_kmajor} b_kmajor={b_kmajor}")
     return out
 
 
@@ -265,7 +320,11 @@ def linear_supported(x: torch.Tensor, weight: torch.Tensor) -> bool:
     if not (x.is_cuda and x.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16 and enabled()):
         return False
     T = x.numel() // x.shape[-1]
-    return supported(T, weight.shape[0], weight.shape[1]) and supported(T, weight.shape[1], weight.shape[0])
+    fout, fin = weight.shape
+    if supported(T, fout, fin) and supported(T, fin, fout):
+        return True
+    # every GEMM of the op on one of the two kernels: the non-256 ones on the edge-tile kernel
+    return edge_enabled() and edge_supported(T, fout, fin)
 
 
 def forward(x2: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -275,7 +334,8 @@ def forward(x2: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor]
     N = weight.shape[0]
     if bias is None:
         return matmul(x2, weight, T, N, fin, True, True)
-    if x2.is_cuda and supported(T, N, fin) and _use_native(T, N, fin, True, True):
+    if x2.is_cuda and ((supported(T, N, fin) and _use_native(T, N, fin, True, True))
+                       or _use_edge(T, N, fin, True, True)):
         return gemm(x2, weight, T, N, fin, True, True, bias=bias)
     return torch.addmm(bias.to(x2.dtype), x2, weight.t())
 

@@ -611,7 +611,7 @@ def gelu_mlp(x: torch.Tensor, w_up: torch.Tensor, b_up: Optional[torch.Tensor], 
 def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None,
            act: Optional[str] = None, side: bool = False) -> torch.Tensor:
     """F.linear on the MFMA GEMM kernel when the shapes fit it (ops/gemm.py: tokens, in and out multiples of 256,
-    bf16, PLX_LM_GEMM != 0), with the weight gradient written into the flat gradient slot when ``weight`` is a flat
+    bf16, PLX_LM_GEMM != 0; with PLX_LM_GEMM_EDGE=1 multiples of 8, on the edge-tile kernel), with the weight gradient written into the flat gradient slot when ``weight`` is a flat
     parameter in lp mode with direct grads; hipBLASLt (F.linear / the direct-gradient form) otherwise.
     ``act="gelu_tanh"`` applies GPT-2's GELU inside the op, so its backward is fused with the bias gradient."""
     if act not in (None, "gelu_tanh"):
