@@ -42,6 +42,8 @@
 #include "handoff.h"
 #include <stdint.h>
 
+#include <initializer_list>
+
 #define PLX_API extern "C" __attribute__((visibility("default")))
 
 namespace {
@@ -55,6 +57,13 @@ struct alignas(16) bf16x8 {
 __device__ __forceinline__ float bf2f(uint16_t b) { return __uint_as_float(((uint32_t)b) << 16); }
 __device__ __forceinline__ uint16_t f2bf(float f) {  // hardware RNE conversion, NaN stays NaN
   return __builtin_bit_cast(uint16_t, (__bf16)f);
+}
+
+// the kernels move 16-byte vectors: every bf16 matrix an entry point takes starts on a 16-byte boundary
+inline bool misaligned16(std::initializer_list<const void*> ps) {
+  uintptr_t bits = 0;
+  for (const void* p : ps) bits |= (uintptr_t)p;
+  return (bits & 15) != 0;
 }
 
 inline int grid_for(int64_t items) {
@@ -489,6 +498,7 @@ __global__ __launch_bounds__(kBlock) void colsum_kernel(const bf16x8* __restrict
 PLX_API int plx_qkv_rope_fwd(const void* qkv, const float* cosv, const float* sinv, void* q, void* k, void* v,
                              int64_t T, int S, int H, int KV, int D, int rot_heads, hipStream_t stream) {
   if (T <= 0 || S <= 0 || T % S || D % 16 || rot_heads < 0 || rot_heads > H + KV) return 1;
+  if (misaligned16({qkv, q, k, v})) return 1;
   const int64_t items = T * (H + 2 * KV) * (D / 16);
   hipLaunchKernelGGL(qkv_rope_fwd_kernel, dim3(grid_for(items)), dim3(kBlock), 0, stream, (const bf16x8*)qkv, cosv,
                      sinv, (bf16x8*)q, (bf16x8*)k, (bf16x8*)v, T, S, H, KV, D, rot_heads);
@@ -498,6 +508,7 @@ PLX_API int plx_qkv_rope_fwd(const void* qkv, const float* cosv, const float* si
 PLX_API int plx_qkv_rope_bwd(const void* dq, const void* dk, const void* dv, const float* cosv, const float* sinv,
                              void* dqkv, int64_t T, int S, int H, int KV, int D, int rot_heads, hipStream_t stream) {
   if (T <= 0 || S <= 0 || T % S || D % 16 || rot_heads < 0 || rot_heads > H + KV) return 1;
+  if (misaligned16({dq, dk, dv, dqkv})) return 1;
   const int64_t items = T * (H + 2 * KV) * (D / 16);
   hipLaunchKernelGGL(qkv_rope_bwd_kernel, dim3(grid_for(items)), dim3(kBlock), 0, stream, (const bf16x8*)dq,
                      (const bf16x8*)dk, (const bf16x8*)dv, cosv, sinv, (bf16x8*)dqkv, T, S, H, KV, D, rot_heads);
@@ -505,14 +516,14 @@ PLX_API int plx_qkv_rope_bwd(const void* dq, const void* dk, const void* dv, con
 }
 
 PLX_API int plx_swiglu_fwd(const void* h, void* a, int64_t T, int F, hipStream_t stream) {
-  if (T <= 0 || F % 8) return 1;
+  if (T <= 0 || F <= 0 || F % 8 || misaligned16({h, a})) return 1;
   hipLaunchKernelGGL(swiglu_fwd_kernel, dim3(grid_for(T * (F / 8))), dim3(kBlock), 0, stream, (const bf16x8*)h,
                      (bf16x8*)a, T, F / 8);
   return (int)hipGetLastError();
 }
 
 PLX_API int plx_swiglu_bwd(const void* da, const void* h, void* dh, int64_t T, int F, hipStream_t stream) {
-  if (T <= 0 || F % 8) return 1;
+  if (T <= 0 || F <= 0 || F % 8 || misaligned16({da, h, dh})) return 1;
   hipLaunchKernelGGL(swiglu_bwd_kernel, dim3(grid_for(T * (F / 8))), dim3(kBlock), 0, stream, (const bf16x8*)da,
                      (const bf16x8*)h, (bf16x8*)dh, T, F / 8);
   return (int)hipGetLastError();
@@ -609,6 +620,7 @@ PLX_API int plx_colsum_splits(int64_t T, int N) {
 PLX_API int plx_colsum(const void* x, int64_t T, int N, float* part, unsigned* cnt, void* out, int mode,
                        hipStream_t stream) {
   if (T <= 0 || N <= 0 || N % 8 || ((uintptr_t)x & 15) || mode < 0 || mode > 2) return 1;
+  if (((uintptr_t)part & 3) || ((uintptr_t)cnt & 3) || ((uintptr_t)out & (mode ? 3 : 1))) return 1;
   const int R0 = plx_colsum_splits(T, N);
   const int rpb = (int)((T + R0 - 1) / R0);
   const int R = (int)((T + rpb - 1) / rpb);
@@ -622,6 +634,7 @@ PLX_API int plx_gelu_bwd_colsum(const void* da, const void* h, void* dh, int64_t
                                 void* out, int mode, hipStream_t stream) {
   if (T <= 0 || N <= 0 || N % 8 || (((uintptr_t)da | (uintptr_t)h | (uintptr_t)dh) & 15) || mode < 0 || mode > 2)
     return 1;
+  if (((uintptr_t)part & 3) || ((uintptr_t)cnt & 3) || ((uintptr_t)out & (mode ? 3 : 1))) return 1;
   const int R0 = plx_colsum_splits(T, N);
   const int rpb = (int)((T + R0 - 1) / R0);
   const int R = (int)((T + rpb - 1) / rpb);
