@@ -121,12 +121,16 @@ class Attention(nn.Module):
         self.proj = nn.Linear(cfg.n_heads * hd, cfg.d_model, bias=cfg.bias)
         self._drop = None  # (AttnDropoutState, layer index): Transformer.set_attn_dropout
         self._window = None  # AttnWindowState: Transformer.set_attn_window
+        self._fp8 = False  # Transformer.set_fp8
 
     def forward(self, x, rope=None):
         B, S, _ = x.shape
         cfg = self.cfg
         hd = cfg.head_dim
-        qkv = lm_ops.linear(x, self.qkv.weight, self.qkv.bias, side=True)
+        if self._fp8:  # the FP8 GEMMs (ops/fp8.py); the projection below too
+            qkv = lm_ops.linear(x, self.qkv.weight, self.qkv.bias, fp8=True)
+        else:
+            qkv = lm_ops.linear(x, self.qkv.weight, self.qkv.bias, side=True)
         if qkv.dtype == torch.bfloat16 and qkv.is_cuda:
             # one HIP pass: split + RoPE + head-major relayout (ops/lm.py)
             q, k, v = lm_ops.qkv_rope(qkv, B, S, cfg.n_heads, cfg.kv_heads, hd, rope)
@@ -150,6 +154,8 @@ class Attention(nn.Module):
             y = flash_attention(q, k, v, causal=True, drop=drop)
         else:
             y = flash_attention(q, k, v, causal=True)
+        if self._fp8:
+            return lm_ops.linear(y.reshape(B, S, cfg.n_heads * hd), self.proj.weight, self.proj.bias, fp8=True)
         return lm_ops.linear(y.reshape(B, S, cfg.n_heads * hd), self.proj.weight, self.proj.bias, side=True)
 
 
@@ -162,8 +168,15 @@ class MLP(nn.Module):
         else:
             self.up = nn.Linear(cfg.d_model, cfg.d_ff, bias=cfg.bias)
         self.down = nn.Linear(cfg.d_ff, cfg.d_model, bias=cfg.bias)
+        self._fp8 = False  # Transformer.set_fp8
 
     def forward(self, x):
+        if self._fp8:  # two FP8 linears (ops/fp8.py), GELU in the first one's epilogue
+            if self.kind == "swiglu":
+                h = lm_ops.swiglu(lm_ops.linear(x, self.up.weight, self.up.bias, fp8=True))
+            else:
+                h = lm_ops.linear(x, self.up.weight, self.up.bias, act="gelu_tanh", fp8=True)
+            return lm_ops.linear(h, self.down.weight, self.down.bias, fp8=True)
         if self.kind == "swiglu":
             h = lm_ops.swiglu(lm_ops.linear(x, self.up.weight, self.up.bias, side=True))
         else:  # GELU inside the op, its backward in the down-projection's data-gradient epilogue (ops/lm.py gelu_mlp)
@@ -230,6 +243,14 @@ class Transformer(nn.Module):
         block's attention sees the last W keys, in training and in ``eval()`` alike.  None: the plain attention call."""
         for blk in self.blocks:
             blk.attn._window = state
+
+    def set_fp8(self, on: bool) -> None:
+        """The blocks' attention and MLP matrices on the FP8 GEMMs (ops/lm.py ``linear(fp8=True)``: E4M3 activations
+        and weights, E5M2 output gradients, per-tensor power-of-two scales on the device).  The embeddings, the head
+        and the norms stay bf16.  GPT-2's MLP then runs as two ``linear`` ops instead of ``gelu_mlp``'s fused class.
+        False: every linear takes the branches it took before."""
+        for blk in self.blocks:
+            blk.attn._fp8 = blk.mlp._fp8 = bool(on)
 
     def init_spec(self):
         """(param, kind, scale) for the fused in-place re-initialiser (GPT-2 / Llama conventions)."""

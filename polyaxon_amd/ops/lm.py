@@ -495,6 +495,91 @@ class _LinearMfma(torch.autograd.Function):
         return dx, dw, db, None, None, None, None
 
 
+class _LinearFp8(torch.autograd.Function):
+    """y = x W^T (+ b) (then GELU with ``act``) with the three GEMMs on the FP8 MFMA kernel (ops/fp8.py,
+    csrc/gemm_fp8.hip): x and W are quantised to E4M3 and the output gradient to E5M2, each with a per-tensor
+    power-of-two scale that stays on the device.  The cast writes every tensor row-major and transposed, so the
+    backward's operands -- W^T for dx, dy^T and x^T for dW -- are K-contiguous; only the transposed FP8 copies of x
+    and W are saved, not the bf16 x.  ``slot``/``flat`` as in :class:`_LinearMfma`."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, slot, flat, act=None):
+        from polyaxon_amd.ops import fp8
+
+        x2 = x.reshape(-1, x.shape[-1]).contiguous()
+        T, fin = x2.shape
+        fout = weight.shape[0]
+        ctx.slot, ctx.flat, ctx.has_bias, ctx.xshape = slot, flat, bias is not None and bias.requires_grad, x.shape
+        ctx.bias, ctx.act, ctx.wdtype = bias, act, weight.dtype
+        xq, xqt, ix = fp8.quantize(x2, fp8.E4M3)
+        wq, wqt, iw = fp8.quantize(weight, fp8.E4M3)
+        y = torch.empty(T, fout, dtype=torch.bfloat16, device=x.device)
+        if act is None:
+            fp8.gemm(xq, fp8.E4M3, ix, wq, iw, T, fout, fin, out=y, bias=bias)
+            ctx.save_for_backward(xqt, wqt, ix, iw)
+        else:  # GELU as a second store of the GEMM epilogue
+            h = torch.empty_like(y)
+            fp8.gemm(xq, fp8.E4M3, ix, wq, iw, T, fout, fin, out=h, bias=bias, gelu_out=y)
+            ctx.save_for_backward(xqt, wqt, ix, iw, h)
+        return y.view(*x.shape[:-1], fout)
+
+    @staticmethod
+    def backward(ctx, dy):
+        from polyaxon_amd.ops import fp8
+
+        xqt, wqt, ix, iw, *h = ctx.saved_tensors
+        fin, T = xqt.shape
+        fout = wqt.shape[1]
+        dz, db = _act_backward(ctx, dy.reshape(-1, fout).contiguous(), h[0] if h else None)
+        dq, dqt, idy = fp8.quantize(dz.contiguous(), fp8.E5M2)
+        dw = None
+        if ctx.slot is not None:  # written, or accumulated for a weight used twice, as _wgrad_into does
+            fp8.gemm(dqt, fp8.E5M2, idy, xqt, ix, fout, fin, T, out=ctx.slot.view(fout, fin),
+                     accumulate=bool(ctx.flat.mark_written(ctx.slot)))
+        elif ctx.needs_input_grad[1]:
+            dw = fp8.gemm(dqt, fp8.E5M2, idy, xqt, ix, fout, fin, T).to(ctx.wdtype)
+        dx = fp8.gemm(dq, fp8.E5M2, idy, wqt, iw, T, fin, fout).view(ctx.xshape) if ctx.needs_input_grad[0] else None
+        return dx, dw, db, None, None, None
+
+
+class _LinearFp8Ref(torch.autograd.Function):
+    """:class:`_LinearFp8` in torch ops (ops/fp8.py quantize_reference: the same scale rule, a round trip through
+    torch's float8 dtypes, fp32 matmuls): what ``linear(fp8=True)`` computes on CPU tensors."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, act=None):
+        from polyaxon_amd.ops import fp8
+
+        x2 = x.reshape(-1, x.shape[-1])
+        xq, ix = fp8.quantize_reference(x2, fp8.E4M3)
+        wq, iw = fp8.quantize_reference(weight, fp8.E4M3)
+        y = (xq @ wq.t()) * (ix * iw)
+        if bias is not None:
+            y = y + bias.float()
+        y = y.to(x.dtype)
+        ctx.save_for_backward(xq, wq, y if act is not None else None)
+        ctx.inv, ctx.xshape, ctx.dtypes = (ix, iw), x.shape, (x.dtype, weight.dtype)
+        ctx.bias_dtype = bias.dtype if bias is not None else None
+        if act is not None:
+            y = F.gelu(y, approximate="tanh")
+        return y.view(*x.shape[:-1], weight.shape[0])
+
+    @staticmethod
+    def backward(ctx, dy):
+        from polyaxon_amd.ops import fp8
+
+        xq, wq, h = ctx.saved_tensors
+        ix, iw = ctx.inv
+        dz = dy.reshape(-1, wq.shape[0])
+        if h is not None:
+            dz = torch.ops.aten.gelu_backward(dz, h, approximate="tanh")
+        db = dz.sum(0, dtype=torch.float32).to(ctx.bias_dtype) if ctx.needs_input_grad[2] else None
+        dq, idy = fp8.quantize_reference(dz, fp8.E5M2)
+        dx = ((dq @ wq) * (idy * iw)).to(ctx.dtypes[0]).view(ctx.xshape) if ctx.needs_input_grad[0] else None
+        dw = ((dq.t() @ xq) * (idy * ix)).to(ctx.dtypes[1]) if ctx.needs_input_grad[1] else None
+        return dx, dw, db, None
+
+
 class _SideJoin(torch.autograd.Function):
     """Identity whose backward makes the main stream wait for every side-stream launch so far (side_stream.join)."""
 
@@ -608,14 +693,33 @@ def gelu_mlp(x: torch.Tensor, w_up: torch.Tensor, b_up: Optional[torch.Tensor], 
     return linear(linear(x, w_up, b_up, act="gelu_tanh"), w_down, b_down)
 
 
+def _linear_fp8(x, weight, bias, act):
+    from polyaxon_amd.ops import fp8
+
+    if (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.bfloat16
+            and torch.is_autocast_enabled("cuda")):
+        x = x.to(torch.bfloat16)
+    if fp8.linear_supported(x, weight):
+        return _LinearFp8.apply(x, weight, bias, *_direct_slot(x, weight), act)
+    if x.is_cuda and x.dtype == torch.bfloat16:
+        raise ValueError(f"linear(fp8=True) needs a contiguous bf16 weight and tokens, in and out multiples of 16, got "
+                         f"x {tuple(x.shape)} and weight {tuple(weight.shape)} ({weight.dtype})")
+    return _LinearFp8Ref.apply(x, weight, bias, act)
+
+
 def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None,
-           act: Optional[str] = None, side: bool = False) -> torch.Tensor:
+           act: Optional[str] = None, side: bool = False, fp8: bool = False) -> torch.Tensor:
     """F.linear on the MFMA GEMM kernel when the shapes fit it (ops/gemm.py: tokens, in and out multiples of 256,
     bf16, PLX_LM_GEMM != 0; with PLX_LM_GEMM_EDGE=1 multiples of 8, on the edge-tile kernel), with the weight gradient written into the flat gradient slot when ``weight`` is a flat
     parameter in lp mode with direct grads; hipBLASLt (F.linear / the direct-gradient form) otherwise.
-    ``act="gelu_tanh"`` applies GPT-2's GELU inside the op, so its backward is fused with the bias gradient."""
+    ``act="gelu_tanh"`` applies GPT-2's GELU inside the op, so its backward is fused with the bias gradient.
+    ``fp8=True``: forward, data gradient and weight gradient on the FP8 MFMA kernel with per-tensor device scales
+    (:class:`_LinearFp8`, ops/fp8.py) for bf16 CUDA tensors whose tokens, in and out are multiples of 16 (anything
+    else there raises); the same arithmetic in torch ops on the CPU."""
     if act not in (None, "gelu_tanh"):
         raise ValueError(f"unknown activation {act!r}")
+    if fp8:
+        return _linear_fp8(x, weight, bias, act)
     if (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.bfloat16
             and torch.is_autocast_enabled("cuda")):
         x = x.to(torch.bfloat16)  # what autocast's F.linear does; here it keeps the LayerNorm outputs on the MFMA path

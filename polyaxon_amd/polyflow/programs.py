@@ -49,6 +49,11 @@ The other programs reject it.
 (ops/optim.py, csrc/muon_kernels.hip; the embeddings and everything 1-D stay on AdamW) with ``muon_lr`` and
 ``muon_momentum`` as per-trial hyper-parameters, 0.02 and 0.95 until a trial sets them.  Not together with
 ``layerwise``.  The other programs reject it.
+
+``gpt2`` and ``gpt2_tiny`` also take ``params: {fp8: true}``: the blocks' attention and MLP linears on the FP8 GEMMs
+(ops/fp8.py, csrc/gemm_fp8.hip: E4M3 activations and weights, E5M2 output gradients, per-tensor power-of-two scales
+computed and kept on the device).  It is part of the program, not a per-trial value, and composes with ``dropout``,
+``attn_dropout``, ``attn_window``, ``muon``, ``lr_schedule`` and ``clip_grad``.  The other programs reject it.
 """
 from __future__ import annotations
 
@@ -177,7 +182,15 @@ def _attn_window(params: Dict[str, Any]) -> bool:
     return bool(params.get("attn_window", False))
 
 
+def _fp8(params: Dict[str, Any]) -> bool:
+    from polyaxon_amd.ops import fp8
+
+    return fp8.validate("fp8", params.get("fp8", False))
+
+
 def _no_dropout(name: str, params: Dict[str, Any]) -> None:
+    if "fp8" in params and _fp8(params):
+        raise ValueError(f"program {name} has no transformer linears: `fp8` is a param of gpt2 / gpt2_tiny only")
     if _dropout(params) or "dropout_seed" in params:
         raise ValueError(f"program {name} has no dropout sites: `dropout` is a param of gpt2 / gpt2_tiny only")
     if _attn_dropout(params):
@@ -351,7 +364,8 @@ def _gpt2(params: Dict[str, Any], device, tiny: bool) -> TrialProgram:
                                loss_hparams=loss_hp, dropout=_dropout(params),
                                dropout_seed=int(params.get("dropout_seed", 0)), attn_dropout=_attn_dropout(params),
                                layerwise=_layerwise(params), attn_window=_attn_window(params),
-                               muon=muon_parameter_names(model) if _muon(params) else None)
+                               muon=muon_parameter_names(model) if _muon(params) else None,
+                               fp8=_fp8(params))
     prog = _with_layerwise(_with_attn_dropout(_with_dropout(_with_loss_hp(_with_schedule(_with_clip(TrialProgram(
         ex, unit_steps=int(params.get("unit_steps", 4 if tiny else 10)),
         window=int(params.get("window", 4)),
@@ -364,6 +378,8 @@ def _gpt2(params: Dict[str, Any], device, tiny: bool) -> TrialProgram:
               "unigram_loss": data.unigram_loss, "chance_loss": data.chance_loss,
               "active_vocab": data.active_vocab}), clip), params), loss_hp), _dropout(params)), _attn_dropout(params)),
         _layerwise(params))
+    if _fp8(params):
+        prog.info["fp8"] = True
     return _with_muon(_with_attn_window(prog, _attn_window(params)), _muon(params))
 
 

@@ -259,6 +259,10 @@ def train_lm(argv=None) -> float:
                     help="sliding-window attention: every query sees its last N keys (ops/attn_window.py: device data "
                          "of the windowed flash-attention kernels, training and evaluation alike); 0: no state, the "
                          "plain kernels")
+    ap.add_argument("--fp8", action="store_true",
+                    help="the blocks' attention and MLP linears on the FP8 GEMMs (ops/fp8.py, csrc/gemm_fp8.hip: E4M3 "
+                         "activations and weights, E5M2 output gradients, per-tensor device scales); off: the bf16 "
+                         "kernels, and the library is never loaded")
     ap.add_argument("--lamb", action="store_true",
                     help="LAMB: AdamW's moments with a layer-wise trust ratio on every matrix "
                          "(csrc/layerwise_kernels.hip); needs every tensor's whole norm, so not with --zero1 / "
@@ -354,6 +358,8 @@ def train_lm(argv=None) -> float:
         from polyaxon_amd.ops.attn_window import AttnWindowState
 
         model.set_attn_window(AttnWindowState(dev, args.attn_window))
+    if args.fp8:
+        model.set_fp8(True)
     metrics = MetricReducer(dev, force_comm=force)  # cross-rank mean of the logged loss (RCCL communicator, GPU)
     g = torch.Generator(device=dev).manual_seed(args.seed + 1000 * info["rank"])
 
