@@ -122,13 +122,14 @@ class Attention(nn.Module):
         self._drop = None  # (AttnDropoutState, layer index): Transformer.set_attn_dropout
         self._window = None  # AttnWindowState: Transformer.set_attn_window
         self._fp8 = False  # Transformer.set_fp8
+        self._fp8_recipe = "tensor"
 
     def forward(self, x, rope=None):
         B, S, _ = x.shape
         cfg = self.cfg
         hd = cfg.head_dim
         if self._fp8:  # the FP8 GEMMs (ops/fp8.py); the projection below too
-            qkv = lm_ops.linear(x, self.qkv.weight, self.qkv.bias, fp8=True)
+            qkv = lm_ops.linear(x, self.qkv.weight, self.qkv.bias, fp8=True, fp8_recipe=self._fp8_recipe)
         else:
             qkv = lm_ops.linear(x, self.qkv.weight, self.qkv.bias, side=True)
         if qkv.dtype == torch.bfloat16 and qkv.is_cuda:
@@ -155,7 +156,7 @@ class Attention(nn.Module):
         else:
             y = flash_attention(q, k, v, causal=True)
         if self._fp8:
-            return lm_ops.linear(y.reshape(B, S, cfg.n_heads * hd), self.proj.weight, self.proj.bias, fp8=True)
+            return lm_ops.linear(y.reshape(B, S, cfg.n_heads * hd), self.proj.weight, self.proj.bias, fp8=True, fp8_recipe=self._fp8_recipe)
         return lm_ops.linear(y.reshape(B, S, cfg.n_heads * hd), self.proj.weight, self.proj.bias, side=True)
 
 
@@ -169,14 +170,15 @@ class MLP(nn.Module):
             self.up = nn.Linear(cfg.d_model, cfg.d_ff, bias=cfg.bias)
         self.down = nn.Linear(cfg.d_ff, cfg.d_model, bias=cfg.bias)
         self._fp8 = False  # Transformer.set_fp8
+        self._fp8_recipe = "tensor"
 
     def forward(self, x):
         if self._fp8:  # two FP8 linears (ops/fp8.py), GELU in the first one's epilogue
             if self.kind == "swiglu":
-                h = lm_ops.swiglu(lm_ops.linear(x, self.up.weight, self.up.bias, fp8=True))
+                h = lm_ops.swiglu(lm_ops.linear(x, self.up.weight, self.up.bias, fp8=True, fp8_recipe=self._fp8_recipe))
             else:
-                h = lm_ops.linear(x, self.up.weight, self.up.bias, act="gelu_tanh", fp8=True)
-            return lm_ops.linear(h, self.down.weight, self.down.bias, fp8=True)
+                h = lm_ops.linear(x, self.up.weight, self.up.bias, act="gelu_tanh", fp8=True, fp8_recipe=self._fp8_recipe)
+            return lm_ops.linear(h, self.down.weight, self.down.bias, fp8=True, fp8_recipe=self._fp8_recipe)
         if self.kind == "swiglu":
             h = lm_ops.swiglu(lm_ops.linear(x, self.up.weight, self.up.bias, side=True))
         else:  # GELU inside the op, its backward in the down-projection's data-gradient epilogue (ops/lm.py gelu_mlp)
@@ -244,13 +246,18 @@ class Transformer(nn.Module):
         for blk in self.blocks:
             blk.attn._window = state
 
-    def set_fp8(self, on: bool) -> None:
+    def set_fp8(self, on: bool, recipe: str = "tensor") -> None:
         """The blocks' attention and MLP matrices on the FP8 GEMMs (ops/lm.py ``linear(fp8=True)``: E4M3 activations
         and weights, E5M2 output gradients, per-tensor power-of-two scales on the device).  The embeddings, the head
         and the norms stay bf16.  GPT-2's MLP then runs as two ``linear`` ops instead of ``gelu_mlp``'s fused class.
-        False: every linear takes the branches it took before."""
+        ``recipe="mx"``: one E8M0 scale per 32 values instead (``linear(fp8=True, fp8_recipe="mx")``,
+        csrc/gemm_mxfp8.hip).  False: every linear takes the branches it took before."""
+        from polyaxon_amd.ops import fp8
+
+        recipe = fp8.validate_recipe(recipe)
         for blk in self.blocks:
             blk.attn._fp8 = blk.mlp._fp8 = bool(on)
+            blk.attn._fp8_recipe = blk.mlp._fp8_recipe = recipe
 
     def init_spec(self):
         """(param, kind, scale) for the fused in-place re-initialiser (GPT-2 / Llama conventions)."""

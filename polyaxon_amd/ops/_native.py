@@ -58,6 +58,10 @@ LIBRARIES: Dict[str, dict] = {
     # option is used, built without packed fp32 arithmetic like the other new libraries
     "plx_gemm_fp8": {"sources": ["gemm_fp8.hip"], "kind": "hip", "link": [],
                      "flags": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]},
+    # the MXFP8 (block-scaled) LM GEMM with its one-pass cast (ops/fp8.py, recipe "mx"): a library of its own
+    # (plx_gemm_fp8 stays byte for byte what it was), loaded only when that recipe is used, built like plx_gemm_fp8
+    "plx_gemm_mxfp8": {"sources": ["gemm_mxfp8.hip"], "kind": "hip", "link": [],
+                       "flags": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]},
     "plx_rccl": {"sources": ["rccl_comm.cpp"], "kind": "hip_host", "link": ["-lrccl", "-pthread"]},
 }
 
@@ -390,6 +394,13 @@ SIGNATURES: Dict[str, Dict[str, list]] = {
         "plx_fp8_amax": [_P, _L, _I, _P, _P, _P],
         "plx_fp8_cast": [_P, _P, _P, _I, _I, _I, _P, _P],
     },
+    "plx_gemm_mxfp8": {
+        "plx_gemm_mxfp8": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _I, _P, _P, _P],
+        "plx_gemm_mxfp8_splits": [_I, _I, _I],
+        "plx_gemm_mxfp8_ws": [_I, _I, _I],
+        "plx_gemm_mxfp8_tile": [],
+        "plx_mxfp8_cast": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
+    },
     "plx_attn": {
         "plx_attn_fwd": [_P, _I, _P],
         "plx_attn_bwd": [_P, _I, _P, _P],
@@ -455,7 +466,7 @@ SIGNATURES: Dict[str, Dict[str, list]] = {
 }
 
 
-RESTYPES: Dict[str, object] = {"plx_attn_bwd_workspace": ctypes.c_longlong, "plx_conv_wgrad_workspace": _L, "plx_bn_workspace": _L, "plx_bn_l2_workspace": _L, "plx_partial_colsum_workspace": _L, "plx_stem_bn_pool_bwd_workspace": _L, "plx_gemm_tn_workspace": _L, "plx_gemm256_sk_ws": ctypes.c_longlong, "plx_gemm_edge_ws": ctypes.c_longlong, "plx_gemm_fp8_ws": ctypes.c_longlong,"plx_stem_conv_wgrad_workspace": _L, "plx_pm_create": _P, "plx_pm_destroy": None, "plx_set_tn_v2": None, "plx_set_tn2_stem": None, "plx_set_tn2_c64": None, "plx_set_tn_atomic": None, "plx_bn_set_thin": None, "plx_set_adamw_grid_cap": None, "plx_set_adamw_wide": None, "plx_attn_set_fwd_waves": None, "plx_attn_set_dq_waves": None, "plx_attn_set_dkdv_waves": None, "plx_gemm256_set_split_target": None,
+RESTYPES: Dict[str, object] = {"plx_attn_bwd_workspace": ctypes.c_longlong, "plx_conv_wgrad_workspace": _L, "plx_bn_workspace": _L, "plx_bn_l2_workspace": _L, "plx_partial_colsum_workspace": _L, "plx_stem_bn_pool_bwd_workspace": _L, "plx_gemm_tn_workspace": _L, "plx_gemm256_sk_ws": ctypes.c_longlong, "plx_gemm_edge_ws": ctypes.c_longlong, "plx_gemm_fp8_ws": ctypes.c_longlong, "plx_gemm_mxfp8_ws": ctypes.c_longlong, "plx_stem_conv_wgrad_workspace": _L, "plx_pm_create": _P, "plx_pm_destroy": None, "plx_set_tn_v2": None, "plx_set_tn2_stem": None, "plx_set_tn2_c64": None, "plx_set_tn_atomic": None, "plx_bn_set_thin": None, "plx_set_adamw_grid_cap": None, "plx_set_adamw_wide": None, "plx_attn_set_fwd_waves": None, "plx_attn_set_dq_waves": None, "plx_attn_set_dkdv_waves": None, "plx_gemm256_set_split_target": None,
                                "plx_pm_wake": None, "plx_rccl_init": _P, "plx_rccl_error": ctypes.c_char_p}
 
 

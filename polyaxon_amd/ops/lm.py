@@ -580,6 +580,94 @@ class _LinearFp8Ref(torch.autograd.Function):
         return dx, dw, db, None
 
 
+class _LinearMxFp8(torch.autograd.Function):
+    """:class:`_LinearFp8` on the block-scaled recipe (ops/fp8.py ``mx_*``, csrc/gemm_mxfp8.hip): x and W in E4M3, the
+    output gradient in E5M2, each with one E8M0 scale per 32 values along the axis its GEMM contracts.  One cast per
+    tensor writes the row-major bytes and, quantised on their own along the other axis, the transposed bytes, each
+    with its scale words; no amax pass.  Saved: the transposed FP8 copies of x and W with their scales (plus h with a
+    GELU), not the bf16 x.  ``slot``/``flat`` as in :class:`_LinearMfma`."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, slot, flat, act=None):
+        from polyaxon_amd.ops import fp8
+
+        x2 = x.reshape(-1, x.shape[-1]).contiguous()
+        T, fin = x2.shape
+        fout = weight.shape[0]
+        ctx.slot, ctx.flat, ctx.has_bias, ctx.xshape = slot, flat, bias is not None and bias.requires_grad, x.shape
+        ctx.bias, ctx.act, ctx.wdtype = bias, act, weight.dtype
+        xq, sx, xqt, sqt_x = fp8.mx_quantize(x2, fp8.E4M3)
+        wq, sw, wqt, sqt_w = fp8.mx_quantize(weight, fp8.E4M3)
+        y = torch.empty(T, fout, dtype=torch.bfloat16, device=x.device)
+        if act is None:
+            fp8.mx_gemm(xq, fp8.E4M3, sx, wq, sw, T, fout, fin, out=y, bias=bias)
+            ctx.save_for_backward(xqt, sqt_x, wqt, sqt_w)
+        else:  # GELU as a second store of the GEMM epilogue
+            h = torch.empty_like(y)
+            fp8.mx_gemm(xq, fp8.E4M3, sx, wq, sw, T, fout, fin, out=h, bias=bias, gelu_out=y)
+            ctx.save_for_backward(xqt, sqt_x, wqt, sqt_w, h)
+        return y.view(*x.shape[:-1], fout)
+
+    @staticmethod
+    def backward(ctx, dy):
+        from polyaxon_amd.ops import fp8
+
+        xqt, sqt_x, wqt, sqt_w, *h = ctx.saved_tensors
+        fin, T = xqt.shape
+        fout = wqt.shape[1]
+        dz, db = _act_backward(ctx, dy.reshape(-1, fout).contiguous(), h[0] if h else None)
+        dq, sd, dqt, sqt_d = fp8.mx_quantize(dz.contiguous(), fp8.E5M2)
+        dw = None
+        if ctx.slot is not None:  # written, or accumulated for a weight used twice, as _wgrad_into does
+            fp8.mx_gemm(dqt, fp8.E5M2, sqt_d, xqt, sqt_x, fout, fin, T, out=ctx.slot.view(fout, fin),
+                        accumulate=bool(ctx.flat.mark_written(ctx.slot)))
+        elif ctx.needs_input_grad[1]:
+            dw = fp8.mx_gemm(dqt, fp8.E5M2, sqt_d, xqt, sqt_x, fout, fin, T).to(ctx.wdtype)
+        dx = (fp8.mx_gemm(dq, fp8.E5M2, sd, wqt, sqt_w, T, fin, fout).view(ctx.xshape)
+              if ctx.needs_input_grad[0] else None)
+        return dx, dw, db, None, None, None
+
+
+class _LinearMxFp8Ref(torch.autograd.Function):
+    """:class:`_LinearMxFp8` in torch ops (ops/fp8.py mx_quantize_reference: every operand fake-quantised in blocks of
+    32 along the axis its GEMM contracts, fp32 matmuls): what ``linear(fp8=True, fp8_recipe="mx")`` computes on CPU
+    tensors."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, act=None):
+        from polyaxon_amd.ops import fp8
+
+        x2 = x.reshape(-1, x.shape[-1])
+        y = fp8.mx_quantize_reference(x2, fp8.E4M3)[0] @ fp8.mx_quantize_reference(weight, fp8.E4M3)[0].t()
+        if bias is not None:
+            y = y + bias.float()
+        y = y.to(x.dtype)
+        # the backward's operands are blocked along tokens (x) and along out (W): quantised from the values again
+        ctx.save_for_backward(fp8.mx_quantize_reference(x2.t(), fp8.E4M3)[0],
+                              fp8.mx_quantize_reference(weight.t(), fp8.E4M3)[0], y if act is not None else None)
+        ctx.xshape, ctx.dtypes = x.shape, (x.dtype, weight.dtype)
+        ctx.bias_dtype = bias.dtype if bias is not None else None
+        if act is not None:
+            y = F.gelu(y, approximate="tanh")
+        return y.view(*x.shape[:-1], weight.shape[0])
+
+    @staticmethod
+    def backward(ctx, dy):
+        from polyaxon_amd.ops import fp8
+
+        xqt, wqt, h = ctx.saved_tensors  # [in][tokens], [in][out]
+        dz = dy.reshape(-1, wqt.shape[1])
+        if h is not None:
+            dz = torch.ops.aten.gelu_backward(dz, h, approximate="tanh")
+        db = dz.sum(0, dtype=torch.float32).to(ctx.bias_dtype) if ctx.needs_input_grad[2] else None
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = (fp8.mx_quantize_reference(dz, fp8.E5M2)[0] @ wqt.t()).to(ctx.dtypes[0]).view(ctx.xshape)
+        if ctx.needs_input_grad[1]:
+            dw = (fp8.mx_quantize_reference(dz.t(), fp8.E5M2)[0] @ xqt.t()).to(ctx.dtypes[1])
+        return dx, dw, db, None
+
+
 class _SideJoin(torch.autograd.Function):
     """Identity whose backward makes the main stream wait for every side-stream launch so far (side_stream.join)."""
 
@@ -693,12 +781,20 @@ def gelu_mlp(x: torch.Tensor, w_up: torch.Tensor, b_up: Optional[torch.Tensor], 
     return linear(linear(x, w_up, b_up, act="gelu_tanh"), w_down, b_down)
 
 
-def _linear_fp8(x, weight, bias, act):
+def _linear_fp8(x, weight, bias, act, recipe="tensor"):
     from polyaxon_amd.ops import fp8
 
     if (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.bfloat16
             and torch.is_autocast_enabled("cuda")):
         x = x.to(torch.bfloat16)
+    if fp8.validate_recipe(recipe) == "mx":
+        if fp8.mx_linear_supported(x, weight):
+            return _LinearMxFp8.apply(x, weight, bias, *_direct_slot(x, weight), act)
+        if x.is_cuda and x.dtype == torch.bfloat16:
+            raise ValueError(f"linear(fp8=True, fp8_recipe='mx') needs a contiguous bf16 weight and tokens, in and out "
+                             f"multiples of 32, got x {tuple(x.shape)} and weight {tuple(weight.shape)} "
+                             f"({weight.dtype})")
+        return _LinearMxFp8Ref.apply(x, weight, bias, act)
     if fp8.linear_supported(x, weight):
         return _LinearFp8.apply(x, weight, bias, *_direct_slot(x, weight), act)
     if x.is_cuda and x.dtype == torch.bfloat16:
@@ -708,18 +804,23 @@ def _linear_fp8(x, weight, bias, act):
 
 
 def linear(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None,
-           act: Optional[str] = None, side: bool = False, fp8: bool = False) -> torch.Tensor:
+           act: Optional[str] = None, side: bool = False, fp8: bool = False,
+           fp8_recipe: str = "tensor") -> torch.Tensor:
     """F.linear on the MFMA GEMM kernel when the shapes fit it (ops/gemm.py: tokens, in and out multiples of 256,
     bf16, PLX_LM_GEMM != 0; with PLX_LM_GEMM_EDGE=1 multiples of 8, on the edge-tile kernel), with the weight gradient written into the flat gradient slot when ``weight`` is a flat
     parameter in lp mode with direct grads; hipBLASLt (F.linear / the direct-gradient form) otherwise.
     ``act="gelu_tanh"`` applies GPT-2's GELU inside the op, so its backward is fused with the bias gradient.
     ``fp8=True``: forward, data gradient and weight gradient on the FP8 MFMA kernel with per-tensor device scales
     (:class:`_LinearFp8`, ops/fp8.py) for bf16 CUDA tensors whose tokens, in and out are multiples of 16 (anything
-    else there raises); the same arithmetic in torch ops on the CPU."""
+    else there raises); the same arithmetic in torch ops on the CPU.  ``fp8_recipe="mx"`` (with ``fp8=True`` only):
+    one E8M0 scale per 32 values instead of one per tensor (:class:`_LinearMxFp8`, csrc/gemm_mxfp8.hip), tokens, in
+    and out multiples of 32."""
     if act not in (None, "gelu_tanh"):
         raise ValueError(f"unknown activation {act!r}")
+    if fp8_recipe != "tensor" and not fp8:
+        raise ValueError(f"fp8_recipe={fp8_recipe!r} needs fp8=True")
     if fp8:
-        return _linear_fp8(x, weight, bias, act)
+        return _linear_fp8(x, weight, bias, act, fp8_recipe)
     if (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.bfloat16
             and torch.is_autocast_enabled("cuda")):
         x = x.to(torch.bfloat16)  # what autocast's F.linear does; here it keeps the LayerNorm outputs on the MFMA path

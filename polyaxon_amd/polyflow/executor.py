@@ -54,7 +54,7 @@ class ResidentTrialExecutor:
                  lp_dtype: Optional[torch.dtype] = None, clip_grad: bool = False, lr_schedule=False,
                  loss_hparams: bool = False, dropout: bool = False, dropout_seed: int = 0,
                  attn_dropout: bool = False, layerwise: bool = False, attn_window: bool = False,
-                 muon=None, fp8: bool = False):
+                 muon=None, fp8: bool = False, fp8_recipe: str = "tensor"):
         """``lp_dtype`` (the language models, GPU): the model computes from bf16 weights with bf16 gradients and the
         optimizer keeps the fp32 master (ops/flat.py lp mode); every re-init / restore refreshes the bf16 copy.
         ``clip_grad``: global-norm gradient clipping (ops/optim.py) with ``max_grad_norm`` as one more device
@@ -89,7 +89,9 @@ class ResidentTrialExecutor:
         ``muon`` (``adamw``): names of the weight matrices that get Muon (ops/optim.py, csrc/muon_kernels.hip), with
         ``muon_lr`` and ``muon_momentum`` as two more device hyper-parameters; not together with ``layerwise``.
         ``fp8``: the model's ``set_fp8(True)``: its blocks' linears run the FP8 GEMMs with per-tensor scales that stay
-        on the device (ops/fp8.py), so the step stays capturable.  Part of the program, not a per-trial value."""
+        on the device (ops/fp8.py), so the step stays capturable.  Part of the program, not a per-trial value.
+        ``fp8_recipe``: ``"tensor"`` (that) or ``"mx"`` (one E8M0 scale per 32 values, csrc/gemm_mxfp8.hip); anything
+        but the default needs ``fp8=True``."""
         self.device = torch.device(device)
         self.is_cuda = self.device.type == "cuda"
         if channels_last:
@@ -143,11 +145,13 @@ class ResidentTrialExecutor:
             self.attn_window = AttnWindowState(self.device)
             model.set_attn_window(self.attn_window)
         self.fp8 = bool(fp8)
+        if fp8_recipe != "tensor" and not fp8:
+            raise ValueError("fp8_recipe needs fp8=True")
         if fp8:
             if not hasattr(model, "set_fp8"):
                 raise ValueError(f"fp8=True needs a model with set_fp8(); {type(model).__name__} has no transformer "
                                  "linears")
-            model.set_fp8(True)
+            model.set_fp8(True, fp8_recipe)
         # default: cross entropy of the fp32-cast logits; on the GPU in one fused HIP kernel each way (ops/lm.py
         # class_xent: no fp32 logits copy, log-softmax or NLL kernels between the head GEMM and its backward, where the
         # host launching them was the bottleneck of the forward -> backward hand-off; +0.1-0.2 %, r5_class_xent_ab.jsonl)

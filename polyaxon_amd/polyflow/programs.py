@@ -54,6 +54,9 @@ The other programs reject it.
 (ops/fp8.py, csrc/gemm_fp8.hip: E4M3 activations and weights, E5M2 output gradients, per-tensor power-of-two scales
 computed and kept on the device).  It is part of the program, not a per-trial value, and composes with ``dropout``,
 ``attn_dropout``, ``attn_window``, ``muon``, ``lr_schedule`` and ``clip_grad``.  The other programs reject it.
+``params: {fp8: true, fp8_recipe: mx}`` selects the block-scaled recipe instead (csrc/gemm_mxfp8.hip: one E8M0 scale
+per 32 values, computed in the cast's single pass and applied by the MFMA); ``fp8_recipe`` defaults to ``tensor`` and
+is refused without ``fp8: true``.
 """
 from __future__ import annotations
 
@@ -188,8 +191,19 @@ def _fp8(params: Dict[str, Any]) -> bool:
     return fp8.validate("fp8", params.get("fp8", False))
 
 
+def _fp8_recipe(params: Dict[str, Any]) -> str:
+    from polyaxon_amd.ops import fp8
+
+    if "fp8_recipe" not in params:
+        return "tensor"
+    recipe = fp8.validate_recipe(params["fp8_recipe"])
+    if not _fp8(params):
+        raise ValueError("`fp8_recipe` needs `fp8: true`")
+    return recipe
+
+
 def _no_dropout(name: str, params: Dict[str, Any]) -> None:
-    if "fp8" in params and _fp8(params):
+    if ("fp8" in params and _fp8(params)) or "fp8_recipe" in params:
         raise ValueError(f"program {name} has no transformer linears: `fp8` is a param of gpt2 / gpt2_tiny only")
     if _dropout(params) or "dropout_seed" in params:
         raise ValueError(f"program {name} has no dropout sites: `dropout` is a param of gpt2 / gpt2_tiny only")
@@ -365,7 +379,7 @@ def _gpt2(params: Dict[str, Any], device, tiny: bool) -> TrialProgram:
                                dropout_seed=int(params.get("dropout_seed", 0)), attn_dropout=_attn_dropout(params),
                                layerwise=_layerwise(params), attn_window=_attn_window(params),
                                muon=muon_parameter_names(model) if _muon(params) else None,
-                               fp8=_fp8(params))
+                               fp8=_fp8(params), fp8_recipe=_fp8_recipe(params))
     prog = _with_layerwise(_with_attn_dropout(_with_dropout(_with_loss_hp(_with_schedule(_with_clip(TrialProgram(
         ex, unit_steps=int(params.get("unit_steps", 4 if tiny else 10)),
         window=int(params.get("window", 4)),
@@ -380,6 +394,8 @@ def _gpt2(params: Dict[str, Any], device, tiny: bool) -> TrialProgram:
         _layerwise(params))
     if _fp8(params):
         prog.info["fp8"] = True
+        if _fp8_recipe(params) != "tensor":
+            prog.info["fp8_recipe"] = _fp8_recipe(params)
     return _with_muon(_with_attn_window(prog, _attn_window(params)), _muon(params))
 
 

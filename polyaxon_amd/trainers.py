@@ -263,6 +263,10 @@ def train_lm(argv=None) -> float:
                     help="the blocks' attention and MLP linears on the FP8 GEMMs (ops/fp8.py, csrc/gemm_fp8.hip: E4M3 "
                          "activations and weights, E5M2 output gradients, per-tensor device scales); off: the bf16 "
                          "kernels, and the library is never loaded")
+    ap.add_argument("--fp8-recipe", "--fp8_recipe", dest="fp8_recipe", choices=("tensor", "mx"), default=None,
+                    help="with --fp8: `tensor` (default) = one power-of-two scale per tensor, `mx` = one E8M0 scale per "
+                         "32 values, computed in the cast's single pass and applied by the scaled MFMA "
+                         "(csrc/gemm_mxfp8.hip)")
     ap.add_argument("--lamb", action="store_true",
                     help="LAMB: AdamW's moments with a layer-wise trust ratio on every matrix "
                          "(csrc/layerwise_kernels.hip); needs every tensor's whole norm, so not with --zero1 / "
@@ -358,8 +362,10 @@ def train_lm(argv=None) -> float:
         from polyaxon_amd.ops.attn_window import AttnWindowState
 
         model.set_attn_window(AttnWindowState(dev, args.attn_window))
+    if args.fp8_recipe is not None and not args.fp8:
+        raise SystemExit("--fp8-recipe needs --fp8")
     if args.fp8:
-        model.set_fp8(True)
+        model.set_fp8(True, args.fp8_recipe or "tensor")
     metrics = MetricReducer(dev, force_comm=force)  # cross-rank mean of the logged loss (RCCL communicator, GPU)
     g = torch.Generator(device=dev).manual_seed(args.seed + 1000 * info["rank"])
 
