@@ -51,6 +51,9 @@ class TransformerConfig:
     # their data gradient and the tied-weight gradient are gemm256 shapes); the padded logits carry a -inf bias, so
     # the softmax, the loss and every gradient of the real vocabulary are unchanged and the padded rows get 0
     vocab_multiple: int = int(os.environ.get("PLX_VOCAB_MULTIPLE", "256"))  # A/B knob: 1 = no padding
+    # > 0: every block's MLP is a mixture of this many experts (MoEMLP), each token going to moe_top_k of them
+    n_experts: int = 0
+    moe_top_k: int = 2
 
     @property
     def kv_heads(self) -> int:
@@ -186,13 +189,45 @@ class MLP(nn.Module):
         return lm_ops.linear(h, self.down.weight, self.down.bias, side=True)
 
 
+class _ExpertWeights(nn.Module):
+    """One weight tensor for all experts, [E, out, in]: named ``weight`` so ``init_spec``'s rules see ``up.weight`` /
+    ``down.weight`` / ``router.weight`` as they do for the dense MLP."""
+
+    def __init__(self, *shape: int):
+        super().__init__()
+        self.weight = nn.Parameter(torch.empty(*shape))
+
+
+class MoEMLP(nn.Module):
+    """Mixture-of-experts MLP (ops/moe.py, csrc/gemm_grouped.hip): a fp32 softmax router picks ``moe_top_k`` of
+    ``n_experts`` bias-free experts per token; every expert's projections run in one grouped GEMM each.  ``forward``
+    returns y and leaves the layer's load-balance term in ``aux`` (``Transformer.moe_aux`` sums them)."""
+
+    def __init__(self, cfg: TransformerConfig):
+        super().__init__()
+        self.kind, self.top_k = cfg.mlp, cfg.moe_top_k
+        if not 0 < cfg.moe_top_k <= cfg.n_experts:
+            raise ValueError(f"moe_top_k must be in 1 .. n_experts = {cfg.n_experts}, got {cfg.moe_top_k}")
+        E, d, ff = cfg.n_experts, cfg.d_model, cfg.d_ff
+        self.router = _ExpertWeights(E, d)
+        self.up = _ExpertWeights(E, 2 * ff if cfg.mlp == "swiglu" else ff, d)
+        self.down = _ExpertWeights(E, d, ff)
+        self.aux = None
+
+    def forward(self, x):
+        from polyaxon_amd.ops import moe
+
+        y, self.aux = moe.moe_mlp(x, self.router.weight, self.up.weight, self.down.weight, self.top_k, self.kind)
+        return y
+
+
 class Block(nn.Module):
     def __init__(self, cfg: TransformerConfig):
         super().__init__()
         Norm = (lambda d: RMSNorm(d, cfg.norm_eps)) if cfg.norm == "rmsnorm" else (
             lambda d: _rms.LayerNorm(d, eps=cfg.norm_eps))  # fused bf16 LayerNorm (csrc/rmsnorm.hip)
         self.n1, self.n2 = Norm(cfg.d_model), Norm(cfg.d_model)
-        self.attn, self.mlp = Attention(cfg), MLP(cfg)
+        self.attn, self.mlp = Attention(cfg), (MoEMLP(cfg) if cfg.n_experts > 0 else MLP(cfg))
         self._drop = None  # (DropoutState, layer index): Transformer.set_dropout
 
     def forward(self, x, rope=None):
@@ -255,6 +290,8 @@ class Transformer(nn.Module):
         from polyaxon_amd.ops import fp8
 
         recipe = fp8.validate_recipe(recipe)
+        if on and self.cfg.n_experts > 0:
+            raise ValueError("the experts of a mixture-of-experts MLP have no FP8 path")
         for blk in self.blocks:
             blk.attn._fp8 = blk.mlp._fp8 = bool(on)
             blk.attn._fp8_recipe = blk.mlp._fp8_recipe = recipe
@@ -331,6 +368,11 @@ class Transformer(nn.Module):
         if isinstance(norm, RMSNorm):
             return _rms.add_rms_norm(x, r, norm.weight, norm.eps)
         return _rms.add_layer_norm(x, r, norm.weight, norm.bias, norm.eps)
+
+    def moe_aux(self) -> torch.Tensor:
+        """Sum of the MoE layers' load-balance terms of the last forward (a scalar; 0 for a dense model)"""
+        terms = [blk.mlp.aux for blk in self.blocks if getattr(blk.mlp, "aux", None) is not None]
+        return torch.stack(terms).sum() if terms else torch.zeros((), device=self.embed.weight.device)
 
     def num_params(self) -> int:
         return sum(p.numel() for p in self.parameters())

@@ -62,6 +62,10 @@ LIBRARIES: Dict[str, dict] = {
     # (plx_gemm_fp8 stays byte for byte what it was), loaded only when that recipe is used, built like plx_gemm_fp8
     "plx_gemm_mxfp8": {"sources": ["gemm_mxfp8.hip"], "kind": "hip", "link": [],
                        "flags": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]},
+    # the grouped GEMM of the mixture-of-experts MLP with its gather / combine passes (ops/moe.py): a library of its
+    # own (plx_gemm_edge stays byte for byte what it was), loaded only when MoE is used, built like plx_gemm_edge
+    "plx_gemm_grouped": {"sources": ["gemm_grouped.hip"], "kind": "hip", "link": [],
+                         "flags": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]},
     "plx_rccl": {"sources": ["rccl_comm.cpp"], "kind": "hip_host", "link": ["-lrccl", "-pthread"]},
 }
 
@@ -401,6 +405,16 @@ SIGNATURES: Dict[str, Dict[str, list]] = {
         "plx_gemm_mxfp8_tile": [],
         "plx_mxfp8_cast": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
     },
+    "plx_gemm_grouped": {
+        "plx_gemm_grouped_rows": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _L, _I, _P],
+        "plx_gemm_grouped_wgrad": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
+        "plx_gemm_grouped_check": [_I, _I, _I, _I, _I],
+        "plx_gemm_grouped_rows_blocks": [_I, _I, _I],
+        "plx_gemm_grouped_tile": [],
+        "plx_moe_gather": [_P, _P, _P, _P, _I, _I, _I, _P],
+        "plx_moe_combine": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
+        "plx_moe_gate_grad": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
+    },
     "plx_attn": {
         "plx_attn_fwd": [_P, _I, _P],
         "plx_attn_bwd": [_P, _I, _P, _P],
@@ -466,7 +480,7 @@ SIGNATURES: Dict[str, Dict[str, list]] = {
 }
 
 
-RESTYPES: Dict[str, object] = {"plx_attn_bwd_workspace": ctypes.c_longlong, "plx_conv_wgrad_workspace": _L, "plx_bn_workspace": _L, "plx_bn_l2_workspace": _L, "plx_partial_colsum_workspace": _L, "plx_stem_bn_pool_bwd_workspace": _L, "plx_gemm_tn_workspace": _L, "plx_gemm256_sk_ws": ctypes.c_longlong, "plx_gemm_edge_ws": ctypes.c_longlong, "plx_gemm_fp8_ws": ctypes.c_longlong, "plx_gemm_mxfp8_ws": ctypes.c_longlong, "plx_stem_conv_wgrad_workspace": _L, "plx_pm_create": _P, "plx_pm_destroy": None, "plx_set_tn_v2": None, "plx_set_tn2_stem": None, "plx_set_tn2_c64": None, "plx_set_tn_atomic": None, "plx_bn_set_thin": None, "plx_set_adamw_grid_cap": None, "plx_set_adamw_wide": None, "plx_attn_set_fwd_waves": None, "plx_attn_set_dq_waves": None, "plx_attn_set_dkdv_waves": None, "plx_gemm256_set_split_target": None,
+RESTYPES: Dict[str, object] = {"plx_attn_bwd_workspace": ctypes.c_longlong, "plx_conv_wgrad_workspace": _L, "plx_bn_workspace": _L, "plx_bn_l2_workspace": _L, "plx_partial_colsum_workspace": _L, "plx_stem_bn_pool_bwd_workspace": _L, "plx_gemm_tn_workspace": _L, "plx_gemm256_sk_ws": ctypes.c_longlong, "plx_gemm_edge_ws": ctypes.c_longlong, "plx_gemm_fp8_ws": ctypes.c_longlong, "plx_gemm_mxfp8_ws": ctypes.c_longlong, "plx_gemm_grouped_rows_blocks": ctypes.c_longlong,"plx_stem_conv_wgrad_workspace": _L, "plx_pm_create": _P, "plx_pm_destroy": None, "plx_set_tn_v2": None, "plx_set_tn2_stem": None, "plx_set_tn2_c64": None, "plx_set_tn_atomic": None, "plx_bn_set_thin": None, "plx_set_adamw_grid_cap": None, "plx_set_adamw_wide": None, "plx_attn_set_fwd_waves": None, "plx_attn_set_dq_waves": None, "plx_attn_set_dkdv_waves": None, "plx_gemm256_set_split_target": None,
                                "plx_pm_wake": None, "plx_rccl_init": _P, "plx_rccl_error": ctypes.c_char_p}
 
 

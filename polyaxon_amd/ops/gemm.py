@@ -36,6 +36,10 @@ not ``0``) the dispatch -- :func:`matmul`, :func:`forward`, :func:`dgrad`, :func
 hipBLASLt as before and the library is never loaded.  First numbers (profiles/gemm_edge.md): split-K weight gradients
 and small problems ahead of hipBLASLt (1.07-2.4x), large forwards and data gradients behind (down to 0.60x), and
 behind gemm256 on most 256-multiples -- ``auto`` does not route to it until a per-class rule is made from them.
+
+Grouped GEMMs (:func:`grouped_rows`, :func:`grouped_wgrad`; csrc/gemm_grouped.hip, library ``plx_gemm_grouped``): E
+problems in one launch whose sizes are an int32 offset table in device memory -- the per-expert segments of a
+mixture-of-experts MLP (ops/moe.py).  Loaded only when those are called.
 """
 from __future__ import annotations
 
@@ -378,3 +382,65 @@ def wgrad(dy2: torch.Tensor, x2: torch.Tensor, out: Optional[torch.Tensor] = Non
     if out is not None:
         out = out.view(fout, fin)
     return matmul(dy2, x2, fout, fin, T, False, False, out=out, accumulate=accumulate)
+
+
+# ------------------------------------------------------------------------------------------------ grouped (MoE) GEMMs
+GROUPED_MAX_EXPERTS = 64
+
+
+def grouped_supported(P: int, E: int, N: int, K: int) -> bool:
+    """csrc/gemm_grouped.hip takes a grouped linear with weights [E][N][K] over P packed rows: all three of its GEMMs"""
+    if not (P > 0 and 0 < E <= GROUPED_MAX_EXPERTS and N > 0 and K > 0 and N % 8 == 0 and K % 8 == 0):
+        return False
+    return (_native.size("plx_gemm_grouped", "plx_gemm_grouped_check", P, E, N, K, 0) == 0
+            and _native.size("plx_gemm_grouped", "plx_gemm_grouped_check", P, E, N, K, 1) == 0)
+
+
+def _grouped_operands(a, b, offs, E):
+    if a.dtype != torch.bfloat16 or b.dtype != torch.bfloat16 or not (a.is_contiguous() and b.is_contiguous()):
+        raise ValueError("the grouped GEMM takes contiguous bf16 operands")
+    if offs.dtype != torch.int32 or offs.numel() != E + 1 or not offs.is_contiguous() or offs.device != a.device:
+        raise ValueError(f"offs must be a contiguous int32 [{E + 1}] tensor on the operands' device")
+
+
+def grouped_rows(a: torch.Tensor, b: torch.Tensor, offs: torch.Tensor, N: int, K: int, b_kmajor: bool,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[p][n] = sum_k a[p][k] . B_e(n, k) for p in [offs[e], offs[e + 1]): ``a`` [P][K] bf16, ``b`` [E][N][K] when
+    ``b_kmajor`` else [E][K][N], ``offs`` int32 [E + 1] in device memory (read by the kernel only: no sync, and the
+    launch does not depend on it).  ``out``: a [P][N] bf16 matrix with unit column stride; rows outside every
+    segment keep what they held."""
+    P, E = a.shape[0], b.shape[0]
+    _grouped_operands(a, b, offs, E)
+    if a.dim() != 2 or a.shape[1] != K or b.numel() != E * N * K:
+        raise ValueError(f"operand shapes {tuple(a.shape)}, {tuple(b.shape)} do not match P x {N} x {K}, E = {E}")
+    if out is None:
+        out = torch.empty(P, N, dtype=torch.bfloat16, device=a.device)
+    if out.dtype != torch.bfloat16 or out.shape != (P, N) or out.stride(1) != 1:
+        raise ValueError("out must be a [P][N] bf16 matrix with unit column stride")
+    rc = _native.lib("plx_gemm_grouped").plx_gemm_grouped_rows(
+        a.data_ptr(), b.data_ptr(), out.data_ptr(), offs.data_ptr(), P, E, N, K, K, K if b_kmajor else N,
+        out.stride(0), N * K, int(b_kmajor), _native.current_stream())
+    if rc != 0:
+        raise RuntimeError(f"plx_gemm_grouped_rows failed ({rc}) for P={P} E={E} N={N} K={K} b_kmajor={b_kmajor}")
+    return out
+
+
+def grouped_wgrad(a: torch.Tensor, b: torch.Tensor, offs: torch.Tensor, E: int,
+                  out: Optional[torch.Tensor] = None, out_dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+    """out[e][m][n] = sum over p in [offs[e], offs[e + 1]) of a[p][m] . b[p][n]: ``a`` [P][M], ``b`` [P][N] bf16; the
+    result [E][M][N] is bf16 or fp32 (``out``'s dtype, else ``out_dtype``).  An empty segment gives zeros; a segment is
+    summed whole and in order, so two calls agree bitwise."""
+    _grouped_operands(a, b, offs, E)
+    if a.dim() != 2 or b.dim() != 2 or a.shape[0] != b.shape[0]:
+        raise ValueError(f"operands must be [P][M] and [P][N], got {tuple(a.shape)} and {tuple(b.shape)}")
+    (P, M), N = a.shape, b.shape[1]
+    if out is None:
+        out = torch.empty(E, M, N, dtype=out_dtype, device=a.device)
+    if out.dtype not in (torch.bfloat16, torch.float32) or out.shape != (E, M, N) or not out.is_contiguous():
+        raise ValueError("out must be a contiguous [E][M][N] bf16 or fp32 tensor")
+    rc = _native.lib("plx_gemm_grouped").plx_gemm_grouped_wgrad(
+        a.data_ptr(), b.data_ptr(), out.data_ptr(), offs.data_ptr(), P, E, M, N, M, N,
+        int(out.dtype == torch.float32), _native.current_stream())
+    if rc != 0:
+        raise RuntimeError(f"plx_gemm_grouped_wgrad failed ({rc}) for P={P} E={E} M={M} N={N}")
+    return out

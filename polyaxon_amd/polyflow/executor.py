@@ -54,7 +54,7 @@ class ResidentTrialExecutor:
                  lp_dtype: Optional[torch.dtype] = None, clip_grad: bool = False, lr_schedule=False,
                  loss_hparams: bool = False, dropout: bool = False, dropout_seed: int = 0,
                  attn_dropout: bool = False, layerwise: bool = False, attn_window: bool = False,
-                 muon=None, fp8: bool = False, fp8_recipe: str = "tensor"):
+                 muon=None, fp8: bool = False, fp8_recipe: str = "tensor", aux_loss: Optional[Callable] = None):
         """``lp_dtype`` (the language models, GPU): the model computes from bf16 weights with bf16 gradients and the
         optimizer keeps the fp32 master (ops/flat.py lp mode); every re-init / restore refreshes the bf16 copy.
         ``clip_grad``: global-norm gradient clipping (ops/optim.py) with ``max_grad_norm`` as one more device
@@ -91,7 +91,10 @@ class ResidentTrialExecutor:
         ``fp8``: the model's ``set_fp8(True)``: its blocks' linears run the FP8 GEMMs with per-tensor scales that stay
         on the device (ops/fp8.py), so the step stays capturable.  Part of the program, not a per-trial value.
         ``fp8_recipe``: ``"tensor"`` (that) or ``"mx"`` (one E8M0 scale per 32 values, csrc/gemm_mxfp8.hip); anything
-        but the default needs ``fp8=True``."""
+        but the default needs ``fp8=True``.
+        ``aux_loss``: called with no argument after the forward; the scalar it returns (a mixture-of-experts model's
+        weighted load-balance term) is added to the loss the step trains on, not to the one the metric ring records."""
+        self.aux_loss = aux_loss
         self.device = torch.device(device)
         self.is_cuda = self.device.type == "cuda"
         if channels_last:
@@ -273,11 +276,15 @@ class ResidentTrialExecutor:
             if self.amp_dtype is not None:
                 with torch.autocast("cuda", dtype=self.amp_dtype):
                     out = self.model(self.x)
-                    loss = self.loss_fn(out, self.y)
+                    loss = metric = self.loss_fn(out, self.y)
+                    if self.aux_loss is not None:
+                        loss = loss + self.aux_loss()
                 loss.backward()
             else:
                 out = self.model(self.x)
-                loss = self.loss_fn(out, self.y)
+                loss = metric = self.loss_fn(out, self.y)
+                if self.aux_loss is not None:
+                    loss = loss + self.aux_loss()
                 loss.backward()
         finally:
             if self.wcache is not None:
@@ -291,7 +298,7 @@ class ResidentTrialExecutor:
         self.opt.step_()
         if self.loss_hp is not None:
             self._train_loss.copy_(loss.detach())
-        self._record(loss.detach())
+        self._record(metric.detach())
 
     def _queue_next_batch(self, step_start) -> None:
         """Generate the next batch into the other buffer on the side stream, after ``step_start`` (the main-stream

@@ -57,6 +57,12 @@ computed and kept on the device).  It is part of the program, not a per-trial va
 ``params: {fp8: true, fp8_recipe: mx}`` selects the block-scaled recipe instead (csrc/gemm_mxfp8.hip: one E8M0 scale
 per 32 values, computed in the cast's single pass and applied by the MFMA); ``fp8_recipe`` defaults to ``tensor`` and
 is refused without ``fp8: true``.
+
+``gpt2`` and ``gpt2_tiny`` also take ``params: {moe_experts: N, moe_top_k: K, moe_aux_coef: c}``: every block's MLP
+becomes a mixture of N experts with top-K routing (ops/moe.py, csrc/gemm_grouped.hip: one grouped GEMM per projection
+whose segment sizes stay on the device, so the step stays capturable).  The step trains on NLL + c x the Switch
+load-balance term (c defaults to 0.01); the committed metric stays the plain NLL.  Part of the program, not a per-trial
+value; not together with ``fp8`` or ``muon``.  ``moe_experts: 0`` is the dense model.  The other programs reject it.
 """
 from __future__ import annotations
 
@@ -202,7 +208,27 @@ def _fp8_recipe(params: Dict[str, Any]) -> str:
     return recipe
 
 
+_MOE_KEYS = ("moe_experts", "moe_top_k", "moe_aux_coef")
+
+
+def _moe(params: Dict[str, Any]) -> Tuple[int, int, float]:
+    """(experts, top-k, balance-loss weight); 0 experts = the dense model.  Experts have no FP8 path, and Muon's
+    parameter list would pick up the 2-D router, so both are refused beside it."""
+    experts = int(params.get("moe_experts", 0) or 0)
+    top_k, coef = int(params.get("moe_top_k", 2)), float(params.get("moe_aux_coef", 0.01))
+    if experts < 0 or (experts and not 0 < top_k <= experts) or coef < 0:
+        raise ValueError(f"`moe_experts` must be >= 0, `moe_top_k` in 1 .. moe_experts and `moe_aux_coef` >= 0 "
+                         f"(got {experts}, {top_k}, {coef})")
+    if experts and _fp8(params):
+        raise ValueError("`moe_experts` and `fp8` cannot be combined: the experts have no FP8 path")
+    if experts and _muon(params):
+        raise ValueError("`moe_experts` and `muon` cannot be combined: Muon has no rule for the router and the experts")
+    return experts, top_k, coef
+
+
 def _no_dropout(name: str, params: Dict[str, Any]) -> None:
+    if any(k in params for k in _MOE_KEYS):
+        raise ValueError(f"program {name} has no transformer MLP: `moe_experts` is a param of gpt2 / gpt2_tiny only")
     if ("fp8" in params and _fp8(params)) or "fp8_recipe" in params:
         raise ValueError(f"program {name} has no transformer linears: `fp8` is a param of gpt2 / gpt2_tiny only")
     if _dropout(params) or "dropout_seed" in params:
@@ -348,12 +374,14 @@ def _gpt2(params: Dict[str, Any], device, tiny: bool) -> TrialProgram:
     from polyaxon_amd.polyflow.executor import ResidentTrialExecutor
 
     dev = torch.device(device)
+    experts, top_k, aux_coef = _moe(params)
+    moe = {"n_experts": experts, "moe_top_k": top_k} if experts else {}
     if tiny:
         # heads: 1 gives head_dim 64, the smallest the flash-attention kernels take (2: the fp32 math fallback)
         cfg = gpt2_125m(vocab_size=int(params.get("vocab", 256)), n_layers=2, d_model=64,
-                        n_heads=int(params.get("heads", 2)), d_ff=256, max_seq_len=int(params.get("seq", 32)))
+                        n_heads=int(params.get("heads", 2)), d_ff=256, max_seq_len=int(params.get("seq", 32)), **moe)
     else:
-        cfg = gpt2_125m(vocab_size=int(params.get("vocab", 50257)))
+        cfg = gpt2_125m(vocab_size=int(params.get("vocab", 50257)), **moe)
     batch = int(params.get("batch", 2 if tiny else 16))
     seq = int(params.get("seq", 32 if tiny else 1024))
     task = str(params.get("task", "copy"))
@@ -379,7 +407,9 @@ def _gpt2(params: Dict[str, Any], device, tiny: bool) -> TrialProgram:
                                dropout_seed=int(params.get("dropout_seed", 0)), attn_dropout=_attn_dropout(params),
                                layerwise=_layerwise(params), attn_window=_attn_window(params),
                                muon=muon_parameter_names(model) if _muon(params) else None,
-                               fp8=_fp8(params), fp8_recipe=_fp8_recipe(params))
+                               fp8=_fp8(params), fp8_recipe=_fp8_recipe(params),
+                               # trains on NLL + c * balance term; the metric ring keeps the plain NLL
+                               aux_loss=(lambda: aux_coef * model.moe_aux()) if experts else None)
     prog = _with_layerwise(_with_attn_dropout(_with_dropout(_with_loss_hp(_with_schedule(_with_clip(TrialProgram(
         ex, unit_steps=int(params.get("unit_steps", 4 if tiny else 10)),
         window=int(params.get("window", 4)),
@@ -396,6 +426,8 @@ def _gpt2(params: Dict[str, Any], device, tiny: bool) -> TrialProgram:
         prog.info["fp8"] = True
         if _fp8_recipe(params) != "tensor":
             prog.info["fp8_recipe"] = _fp8_recipe(params)
+    if experts:
+        prog.info["moe"] = {"experts": experts, "top_k": top_k, "aux_coef": aux_coef}
     return _with_muon(_with_attn_window(prog, _attn_window(params)), _muon(params))
 
 

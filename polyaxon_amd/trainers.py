@@ -267,6 +267,15 @@ def train_lm(argv=None) -> float:
                     help="with --fp8: `tensor` (default) = one power-of-two scale per tensor, `mx` = one E8M0 scale per "
                          "32 values, computed in the cast's single pass and applied by the scaled MFMA "
                          "(csrc/gemm_mxfp8.hip)")
+    ap.add_argument("--moe-experts", "--moe_experts", dest="moe_experts", type=int, default=0,
+                    help="every block's MLP as a mixture of N experts (ops/moe.py, csrc/gemm_grouped.hip: one grouped "
+                         "GEMM per projection, segment sizes on the device); 0: the dense MLP, and the library is never "
+                         "loaded; not with --fp8 / --muon")
+    ap.add_argument("--moe-top-k", "--moe_top_k", dest="moe_top_k", type=int, default=2,
+                    help="with --moe-experts: experts per token")
+    ap.add_argument("--moe-aux-coef", "--moe_aux_coef", dest="moe_aux_coef", type=float, default=0.01,
+                    help="with --moe-experts: weight of the load-balance term in the training loss (the logged loss "
+                         "stays the plain NLL)")
     ap.add_argument("--lamb", action="store_true",
                     help="LAMB: AdamW's moments with a layer-wise trust ratio on every matrix "
                          "(csrc/layerwise_kernels.hip); needs every tensor's whole norm, so not with --zero1 / "
@@ -294,6 +303,10 @@ def train_lm(argv=None) -> float:
                       or os.environ.get("PLX_OPT_IN_BACKWARD", "0") == "1"):
         ap.error("--muon needs every weight matrix's whole update before any step: it cannot be combined with "
                  "--lamb / --zero1 / PLX_ZERO1=1 / PLX_OPT_IN_BACKWARD=1 (AdamW per bucket inside the backward)")
+    if args.moe_experts and (args.fp8 or args.muon):
+        ap.error("--moe-experts cannot be combined with --fp8 (the experts have no FP8 path) or --muon (it has no rule "
+                 "for the router and the experts)")
+    moe = {"n_experts": args.moe_experts, "moe_top_k": args.moe_top_k} if args.moe_experts else {}
     # the process group is the gloo rendezvous; every device collective of the trial (gradient buckets, ZeRO-1,
     # the parameter broadcast, the metric mean) runs on ONE framework RCCL communicator (parallel/comm.py)
     cuda = not args.cpu and torch.cuda.is_available()
@@ -313,7 +326,7 @@ def train_lm(argv=None) -> float:
 
         apply_hbm_budget(dev)
     cfg = {"gpt2_125m": gpt2_125m, "llama3_8b": llama3_8b, "tiny": tiny_llama}[args.model](
-        checkpoint=args.checkpoint_activations)
+        checkpoint=args.checkpoint_activations, **moe)
     seq = min(args.seq, cfg.max_seq_len)
     torch.manual_seed(args.seed)
     model = Transformer(cfg) if dev.type == "cpu" else _build_on_device(Transformer, cfg, dev)
@@ -403,12 +416,16 @@ def train_lm(argv=None) -> float:
                 loss = lm_loss(model(tokens), tokens)
             else:  # trains on the smoothed loss; the logged one is the plain NLL the loss leaves in loss_hp.nll
                 loss = lm_loss(model(tokens), tokens, loss_hp=loss_hp, n_classes=cfg.vocab_size)
+            nll = loss
+            if moe:  # trains on NLL + c x the load-balance term; the logged loss stays the NLL
+                loss = loss + args.moe_aux_coef * model.moe_aux()
         loss.backward()
         ddp.finish()
         opt.step_()
         step += 1
         if (it + 1) % args.log_every == 0 or it == args.steps - 1:
             train_loss = loss
+            loss = nll
             if loss_hp is not None:
                 loss = loss_hp.nll
             loss_mean = metrics.mean(loss)  # every rank joins the collective; rank 0 logs it
