@@ -94,14 +94,46 @@ struct AttnWinDropArgs {
   const int32_t* win;
 };
 
-template <bool DROP, bool WIN = false>
-using KArgs = std::conditional_t<WIN, std::conditional_t<DROP, AttnWinDropArgs, AttnWinArgs>,
-                                 std::conditional_t<DROP, AttnDropArgs, AttnArgs>>;
+// ------------------------------------------------------------------------------------------ document mask
+// Causal self-attention inside the documents packed into one row (ops/attn_doc.py AttnDocState): query i of batch row
+// b sees key j iff start[b][i] <= j <= i.  start / end are int32 [B][S] device tables shared by the heads: start[b][i]
+// the first position of i's document (non-decreasing, <= i), end[b][j] one past the last position of j's document
+// (non-decreasing, > j).  They are read at run time, so one captured step follows the batch.  S == Skv, and every real
+// query keeps its diagonal key: no row is fully masked and lse2 stays finite.  The forward and dQ kernels read start
+// (a lane owns a query), the dK/dV kernel reads end (a lane owns a key): monotone tables put the extreme of a wave or
+// a block at its first or last entry.  Table values only meet comparisons and, clamped to [0, S], loop bounds; every
+// table index is clamped into the row -- a malformed table gives wrong numbers, never an address out of range.  With
+// one document per row (start = 0, end = S) the kernels visit the plain kernels' tiles in their order and leave their
+// bits.  8 waves only.
+struct AttnDocArgs {
+  AttnArgs a;
+  const int32_t *start, *end;
+};
+
+struct AttnDocDropArgs {
+  AttnDropArgs d;
+  const int32_t *start, *end;
+};
+
+template <bool DROP, bool WIN = false, bool DOC = false>
+using KArgs = std::conditional_t<DOC, std::conditional_t<DROP, AttnDocDropArgs, AttnDocArgs>,
+                                 std::conditional_t<WIN, std::conditional_t<DROP, AttnWinDropArgs, AttnWinArgs>,
+                                                    std::conditional_t<DROP, AttnDropArgs, AttnArgs>>>;
 
 __host__ __device__ __forceinline__ const AttnArgs& attn_args(const AttnArgs& ka) { return ka; }
 __host__ __device__ __forceinline__ const AttnArgs& attn_args(const AttnDropArgs& ka) { return ka.a; }
 __host__ __device__ __forceinline__ const AttnArgs& attn_args(const AttnWinArgs& ka) { return ka.a; }
 __host__ __device__ __forceinline__ const AttnArgs& attn_args(const AttnWinDropArgs& ka) { return ka.d.a; }
+__host__ __device__ __forceinline__ const AttnArgs& attn_args(const AttnDocArgs& ka) { return ka.a; }
+__host__ __device__ __forceinline__ const AttnArgs& attn_args(const AttnDocDropArgs& ka) { return ka.d.a; }
+
+// DOC: entry min(i, S - 1) of one batch row of a table (0 <= i: positions past the sequence read the last entry)
+__device__ __forceinline__ int doc_at(const int32_t* row, int i, int S) { return row[min(i, S - 1)]; }
+
+// the same for a wave-uniform i: the value in a scalar register
+__device__ __forceinline__ int doc_at_uniform(const int32_t* row, int i, int S) {
+  return __builtin_amdgcn_readfirstlane(doc_at(row, i, S));
+}
 
 // W of this launch, clamped to S: a window of S keys or more removes nothing, and every bound below stays < 2 S + 256
 __device__ __forceinline__ int win_load(const int32_t* win, int S) {
@@ -120,6 +152,7 @@ __device__ __forceinline__ Drop drop_load(const AttnDropArgs& ka, int bh) {
 }
 
 __device__ __forceinline__ Drop drop_load(const AttnWinDropArgs& ka, int bh) { return drop_load(ka.d, bh); }
+__device__ __forceinline__ Drop drop_load(const AttnDocDropArgs& ka, int bh) { return drop_load(ka.d, bh); }
 
 // the four words of block (qb, kb) = (q >> 2, k >> 2)
 __device__ __forceinline__ void drop_block(const Drop& d, uint32_t qb, uint32_t kb, uint32_t (&c)[4]) {
@@ -306,6 +339,19 @@ __device__ __forceinline__ int win_first_tile(char* smem, const __bf16* K, const
   return j0;
 }
 
+// DOC, forward and dQ: the same for the document mask.  start is non-decreasing, so the block's first query q0 holds
+// the smallest document start of the block; clamped to [0, q0], so j0 * 64 <= q0 < S = Skv whatever the table holds.
+template <int D, int NW>
+__device__ __forceinline__ int doc_first_tile(char* smem, const __bf16* K, const __bf16* V, const AttnArgs& a, int q0,
+                                              const int32_t* start, int wave, int lane) {
+  constexpr int TB = 64 * 2 * D;
+  const int j0 = min(max(doc_at_uniform(start, q0, a.S), 0), q0) / 64;
+  char* fb = smem + (j0 & 1) * 2 * TB;
+  stage_tile<D, 64, NW>(fb, K + (long long)j0 * 64 * a.sk.s, a.sk.s, a.Skv - j0 * 64, a.zero, wave, lane);
+  stage_tile<D, 64, NW>(fb + TB, V + (long long)j0 * 64 * a.sv.s, a.sv.s, a.Skv - j0 * 64, a.zero, wave, lane);
+  return j0;
+}
+
 struct QBlock {
   int b, hq, hk, q0;
 };
@@ -345,9 +391,17 @@ constexpr float RESCALE_TH = 8.f;
 // the tiles that straddle a window start.  A lane can meet a tile wholly before its own window (its wave's earlier
 // queries need it) ahead of its first visible key: every score is -inf, m_run stays -inf (msub = 0, p = 2^-inf = 0),
 // and the first finite maximum rescales the still-zero o and l by alpha = 0.
-template <int D, int NW, bool DROP, bool WIN = false>
-__global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd_kernel(KArgs<DROP, WIN> ka) {
+//
+// DOC (the document mask above): each lane keeps the document start of its query in a register, the wave those of its
+// first and last real query in scalar registers.  The tile loop starts at the tile of the block's smallest start; a
+// wave skips the tiles that end before its first query's document and masks key < start[query] on the tiles that
+// begin before its last query's document -- with the causal and ragged terms one unsigned compare per element, as
+// for the window: a three-term mask cost the one-document call 7-9 % (profiles/attn_doc.md).  A lane can meet a tile wholly before its own document (its wave's earlier
+// queries need it): the argument of the window holds word for word.
+template <int D, int NW, bool DROP, bool WIN = false, bool DOC = false>
+__global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd_kernel(KArgs<DROP, WIN, DOC> ka) {
   static_assert(!WIN || NW == 8, "the windowed kernels exist in the 8-wave form only");
+  static_assert(!DOC || (NW == 8 && !WIN), "the document kernels exist in the 8-wave form only, without a window");
   constexpr int QB = 32 * NW, TB = 64 * 2 * D, STAGE = 2 * TB, ND = D / 32, NS = D / 16;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const AttnArgs& a = attn_args(ka);
@@ -363,9 +417,18 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd_kernel(KArg
   const int kv_end = a.causal ? min(a.Skv, blk.q0 + QB) : a.Skv;
   const int nt = (kv_end + 63) / 64;
   int W = 0, j0 = 0;
+  int ds = 0, ds_first = 0, ds_last = 0;  // DOC: the document start of this lane's query, of the wave's first / last
+  unsigned dspan = 0;                     // DOC: the number of keys this lane's query sees, from ds on
   if constexpr (WIN) {
     W = win_load(ka.win, a.S);
     j0 = win_first_tile<D, NW>(smem, K, V, a, blk.q0, W, wave, lane);
+  } else if constexpr (DOC) {
+    const int32_t* start = ka.start + (long long)blk.b * a.S;
+    ds = min(max(doc_at(start, qi, a.S), 0), a.S);
+    dspan = (unsigned)max(0, min(qi, a.Skv - 1) - ds + 1);
+    ds_first = doc_at_uniform(start, q0w, a.S);
+    ds_last = doc_at_uniform(start, q0w + 31, a.S);
+    j0 = doc_first_tile<D, NW>(smem, K, V, a, blk.q0, start, wave, lane);
   } else {
     stage_tile<D, 64, NW>(smem, K, a.sk.s, a.Skv, a.zero, wave, lane);
     stage_tile<D, 64, NW>(smem + TB, V, a.sv.s, a.Skv, a.zero, wave, lane);
@@ -392,8 +455,9 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd_kernel(KArg
     }
     const char* Ks = smem + (j & 1) * STAGE;
     const char* Vs = Ks + TB;
-    // wave-uniform: tile entirely in this wave's causal future, or (WIN) entirely before its first query's window
-    if (!(a.causal && kv0 > q0w + 31) && !(WIN && kv0 + 63 < q0w - W + 1)) {
+    // wave-uniform: tile entirely in this wave's causal future, or (WIN) entirely before its first query's window, or
+    // (DOC) entirely before its first query's document
+    if (!(a.causal && kv0 > q0w + 31) && !(WIN && kv0 + 63 < q0w - W + 1) && !(DOC && kv0 + 63 < ds_first)) {
       uint32_t keep = 0xffffffffu;
       if constexpr (DROP) {
         if (drop.T != 0) keep = drop_keep_tile(drop, qi, (kv0 >> 2) + h);  // wave-uniform
@@ -404,8 +468,10 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd_kernel(KArg
         st[0] = mfma(row_frag<D>(Ks, ql, 2 * s + h), qf[s], st[0]);
         st[1] = mfma(row_frag<D>(Ks, 32 + ql, 2 * s + h), qf[s], st[1]);
       }
-      // diagonal / ragged tile, or (WIN) one that starts before the window of the wave's last query: mask (raw scores)
-      if ((a.causal && kv0 + 63 > q0w) || kv0 + 64 > a.Skv || (WIN && kv0 < q0w + 31 - W + 1)) {
+      // diagonal / ragged tile, or (WIN) one that starts before the window of the wave's last query, or (DOC) before
+      // the document of its last real query: mask (raw scores)
+      if ((a.causal && kv0 + 63 > q0w) || kv0 + 64 > a.Skv || (WIN && kv0 < q0w + 31 - W + 1) ||
+          (DOC && kv0 < ds_last)) {
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -413,6 +479,8 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd_kernel(KArg
             const int key = kv0 + 32 * t + acc_row(r, h);
             if constexpr (WIN) {  // visible iff qi - W < key <= min(qi, Skv - 1): one unsigned range test
               if ((unsigned)(key - (qi - W + 1)) >= (unsigned)max(0, min(qi, a.Skv - 1) - qi + W)) st[t][r] = NEG_INF;
+            } else if constexpr (DOC) {  // visible iff ds <= key <= min(qi, Skv - 1): the same kind of test
+              if ((unsigned)(key - ds) >= dspan) st[t][r] = NEG_INF;
             } else {
               if ((a.causal && key > qi) || key >= a.Skv) st[t][r] = NEG_INF;
             }
@@ -476,10 +544,11 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_fwd_kernel(KArg
 // ------------------------------------------------------------------------------------------- backward: dQ
 // NW waves x 32 queries per workgroup: the K / V tile in LDS serves NW * 32 query rows (see the forward).  Also
 // produces delta[b][h][q] = sum_d dO . O of its rows (read from the stored bf16 O) for itself and the dK/dV kernel.
-// WIN: the forward's loop start, skip and element mask (p = 0 at the same elements).
-template <int D, int NW, bool DROP, bool WIN = false>
-__global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_bwd_dq_kernel(KArgs<DROP, WIN> ka) {
+// WIN, DOC: the forward's loop start, skip and element mask (p = 0 at the same elements).
+template <int D, int NW, bool DROP, bool WIN = false, bool DOC = false>
+__global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_bwd_dq_kernel(KArgs<DROP, WIN, DOC> ka) {
   static_assert(!WIN || NW == 8, "the windowed kernels exist in the 8-wave form only");
+  static_assert(!DOC || (NW == 8 && !WIN), "the document kernels exist in the 8-wave form only, without a window");
   constexpr int QB = 32 * NW, TB = 64 * 2 * D, STAGE = 2 * TB, ND = D / 32, NS = D / 16;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const AttnArgs a = attn_args(ka);  // a copy: the plain instantiation then keeps the instruction stream it had
@@ -493,9 +562,18 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_bwd_dq_kernel(K
   const int kv_end = a.causal ? min(a.Skv, blk.q0 + QB) : a.Skv;
   const int nt = (kv_end + 63) / 64;
   int W = 0, j0 = 0;
+  int ds = 0, ds_first = 0, ds_last = 0;  // DOC: the document start of this lane's query, of the wave's first / last
+  unsigned dspan = 0;                     // DOC: the number of keys this lane's query sees, from ds on
   if constexpr (WIN) {
     W = win_load(ka.win, a.S);
     j0 = win_first_tile<D, NW>(smem, K, V, a, blk.q0, W, wave, lane);
+  } else if constexpr (DOC) {
+    const int32_t* start = ka.start + (long long)blk.b * a.S;
+    ds = min(max(doc_at(start, qi, a.S), 0), a.S);
+    dspan = qi < a.S ? (unsigned)max(0, min(qi, a.Skv - 1) - ds + 1) : 0u;  // a padded query row sees nothing
+    ds_first = doc_at_uniform(start, q0w, a.S);
+    ds_last = doc_at_uniform(start, q0w + 31, a.S);
+    j0 = doc_first_tile<D, NW>(smem, K, V, a, blk.q0, start, wave, lane);
   } else {
     stage_tile<D, 64, NW>(smem, K, a.sk.s, a.Skv, a.zero, wave, lane);
     stage_tile<D, 64, NW>(smem + TB, V, a.sv.s, a.Skv, a.zero, wave, lane);
@@ -542,7 +620,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_bwd_dq_kernel(K
     }
     const char* Ks = smem + (j & 1) * STAGE;
     const char* Vs = Ks + TB;
-    if (!(a.causal && kv0 > q0w + 31) && !(WIN && kv0 + 63 < q0w - W + 1)) {
+    if (!(a.causal && kv0 > q0w + 31) && !(WIN && kv0 + 63 < q0w - W + 1) && !(DOC && kv0 + 63 < ds_first)) {
       uint32_t keep = 0xffffffffu;
       if constexpr (DROP) {
         if (drop.T != 0) keep = drop_keep_tile(drop, qi, (kv0 >> 2) + h);  // wave-uniform
@@ -556,7 +634,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_bwd_dq_kernel(K
           dp[t] = mfma(row_frag<D>(Vs, 32 * t + ql, 2 * s + h), gf[s], dp[t]);
         }
       const bool mask = (a.causal && kv0 + 63 > q0w) || kv0 + 64 > a.Skv || qi >= a.S ||
-                        (WIN && kv0 < q0w + 31 - W + 1);
+                        (WIN && kv0 < q0w + 31 - W + 1) || (DOC && kv0 < ds_last);
       if constexpr (DROP) {  // dP^T = c M o (V dO^T), before the subtraction of delta
 #pragma unroll
         for (int t = 0; t < 2; ++t)
@@ -573,6 +651,8 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void attn_bwd_dq_kernel(K
             if constexpr (WIN) {  // the forward's range test; a padded query row (qi >= S) sees nothing
               const int span = qi < a.S ? min(qi, a.Skv - 1) - qi + W : 0;
               if ((unsigned)(key - (qi - W + 1)) >= (unsigned)max(0, span)) p = 0.f;
+            } else if constexpr (DOC) {  // the forward's range test
+              if ((unsigned)(key - ds) >= dspan) p = 0.f;
             } else if ((a.causal && key > qi) || key >= a.Skv || qi >= a.S) p = 0.f;
           }
           st[t][r] = p * (dp[t][r] - dlt);  // dS^T (softmax_scale applied at the end)
@@ -746,8 +826,14 @@ __global__ __launch_bounds__(NT, 1) void attn_bwd_dkdv_kernel(AttnArgs a, float*
 // are staged through that region one tensor at a time.
 // WIN: the query sweep ends with the last query that still sees the block's last key; a wave skips the sub-tiles past
 // the last query that sees its last key and masks key <= query - W where a window start crosses its keys.
-template <int D, bool DROP, bool WIN = false>
-__global__ __launch_bounds__(512, 1) void attn_bwd_dkdv8_kernel(KArgs<DROP, WIN> ka, float* __restrict__ ws) {
+// DOC: the transpose of the forward.  Each lane keeps the number of queries that see its key (up to the end of the
+// key's document) in a register, the wave the document ends of its first and last real key in scalar registers; end
+// is non-decreasing, so the sweep of the block ends at the end of its last real key's document, a wave skips the
+// sub-tiles at or past the end of its last key's document and masks query >= end[key] where a sub-tile reaches the
+// end of its first key's document.
+template <int D, bool DROP, bool WIN = false, bool DOC = false>
+__global__ __launch_bounds__(512, 1) void attn_bwd_dkdv8_kernel(KArgs<DROP, WIN, DOC> ka, float* __restrict__ ws) {
+  static_assert(!(WIN && DOC), "the document kernels have no window");
   constexpr int NW = 8, KBLK = 32 * NW, QTB = 64 * 2 * D, QSTAGE = 2 * QTB + 512, ND = D / 32, NS = D / 16;
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const AttnArgs& a = attn_args(ka);
@@ -768,9 +854,19 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_dkdv8_kernel(KArgs<DROP, WIN>
   const long long srow0 = ((long long)b * a.H + hq) * a.S;
   const int qt0 = a.causal ? k0 / 64 : 0;
   int W = 0, q_end = a.S;
+  int de_first = 0, de_last = 0;  // DOC: the document ends of the wave's first / last real key
+  unsigned kspan = 0;             // DOC: the number of queries that see this lane's key, from the key on
   if constexpr (WIN) {
     W = win_load(ka.win, a.S);
     q_end = min(a.S, k0 + KBLK + W - 1);
+  }
+  if constexpr (DOC) {
+    const int32_t* end = ka.end + (long long)b * a.S;
+    const int de = min(max(doc_at(end, kw0 + kl, a.S), 0), a.S);
+    kspan = kw0 + kl < a.Skv ? (unsigned)max(0, de - (kw0 + kl)) : 0u;  // a padded key is seen by nothing
+    de_first = doc_at_uniform(end, kw0, a.S);
+    de_last = doc_at_uniform(end, kw0 + 31, a.S);
+    q_end = min(max(doc_at_uniform(end, k0 + KBLK - 1, a.S), 0), a.S);
   }
   const int total = (q_end + 63) / 64 - qt0;
   auto stage_q = [&](int buf, int it) {
@@ -815,6 +911,7 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_dkdv8_kernel(KArgs<DROP, WIN>
       const int q0 = (qt0 + it) * 64 + 32 * sub;
       if (a.causal && q0 + 31 < kw0) continue;  // wave-uniform: every query precedes this wave's keys
       if (WIN && q0 > kw0 + 31 + W - 1) continue;  // wave-uniform: every query's window starts past this wave's keys
+      if (DOC && q0 >= de_last) continue;  // wave-uniform: every query lies past the documents of this wave's keys
       uint32_t keep = 0xffffu;
       if constexpr (DROP) {
         if (drop.T != 0) keep = drop_keep_sub(drop, (q0 >> 2) + h, key);  // wave-uniform
@@ -826,7 +923,7 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_dkdv8_kernel(KArgs<DROP, WIN>
         dp = mfma(row_frag<D>(Gs, 32 * sub + kl, 2 * s + h), row_frag<D>(Vimg, 32 * wave + kl, 2 * s + h), dp);
       }
       const bool mask = (a.causal && kw0 + 31 > q0) || q0 + 32 > a.S || kw0 + 32 > a.Skv ||
-                        (WIN && q0 + 31 - W + 1 > kw0);
+                        (WIN && q0 + 31 - W + 1 > kw0) || (DOC && q0 + 31 >= de_first);
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const float4 l4 = *(const float4*)(st_lse + 32 * sub + 8 * g + 4 * h);
@@ -840,6 +937,8 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_dkdv8_kernel(KArgs<DROP, WIN>
             const int q = q0 + 8 * g + 4 * h + e;
             if constexpr (WIN) {  // visible iff key <= q < min(key + W, S): one unsigned range test
               if ((unsigned)(q - key) >= (unsigned)(key < a.Skv ? min(W, a.S - key) : 0)) p = 0.f;
+            } else if constexpr (DOC) {  // visible iff key <= q < min(end[key], S): the same kind of test
+              if ((unsigned)(q - key) >= kspan) p = 0.f;
             } else if ((a.causal && key > q) || q >= a.S || key >= a.Skv) p = 0.f;
           }
           if constexpr (DROP) {
@@ -973,7 +1072,77 @@ bool drop_ok(const AttnArgs& a, const uint32_t* hp, const int32_t* step, int lay
 
 }  // namespace
 
-#ifndef PLX_ATTN_WIN  // libplx_attn: the plain and the dropout entry points
+#if defined(PLX_ATTN_DOC)  // libplx_attn_doc (-DPLX_ATTN_DOC): the document-mask entry points, a library of its own
+
+template <int D, bool DROP>
+int launch_doc_fwd(const KArgs<DROP, false, true>& ka, hipStream_t stream) {
+  constexpr int LDS = 4 * 64 * 2 * D;  // 2 stages x {K, V} x 64 rows
+  static int once = prepare(attn_fwd_kernel<D, 8, DROP, false, true>, LDS);
+  if (once) return once;
+  const AttnArgs& a = attn_args(ka);
+  const int grid = ((a.S + 255) / 256) * a.H * a.B;
+  hipLaunchKernelGGL((attn_fwd_kernel<D, 8, DROP, false, true>), dim3(grid), dim3(512), LDS, stream, ka);
+  return (int)hipGetLastError();
+}
+
+template <int D, bool DROP>
+int launch_doc_bwd(const KArgs<DROP, false, true>& ka, float* ws, hipStream_t stream) {
+  constexpr int QLDS = 4 * 64 * 2 * D, KLDS8 = 256 * 2 * D + 2 * (2 * 64 * 2 * D + 512);
+  static_assert(KLDS8 - 256 * 2 * D >= 256 * D * 2, "the dK / dV output staging must fit the stage region");
+  static int once = prepare(attn_bwd_dq_kernel<D, 8, DROP, false, true>, QLDS) |
+                    prepare(attn_bwd_dkdv8_kernel<D, DROP, false, true>, KLDS8);
+  if (once) return once;
+  const AttnArgs& a = attn_args(ka);
+  const int grid = ((a.S + 255) / 256) * a.H * a.B;  // S == Skv: query blocks and key blocks alike
+  // the dQ kernel goes first: it writes delta, which the dK/dV kernel reads
+  hipLaunchKernelGGL((attn_bwd_dq_kernel<D, 8, DROP, false, true>), dim3(grid), dim3(512), QLDS, stream, ka);
+  hipLaunchKernelGGL((attn_bwd_dkdv8_kernel<D, DROP, false, true>), dim3(grid), dim3(512), KLDS8, stream, ka, ws);
+  if (a.H != a.Hkv) {
+    const long long n8 = (long long)a.B * a.Hkv * a.Skv * (D / 8);
+    const int rgrid = (int)std::min<long long>((n8 + NT - 1) / NT, 2048);
+    hipLaunchKernelGGL(attn_bwd_reduce_kernel<D>, dim3(rgrid), dim3(NT), 0, stream, a, (const float*)ws);
+  }
+  return (int)hipGetLastError();
+}
+
+// The plain entry points' checks, plus: both tables present, causal self-attention (S == Skv).  hp and step are both
+// null (no dropout) or both present (attention dropout inside the documents, plx_attn_drop_*'s checks).  A refused call
+// launches nothing.
+static bool doc_ok(const AttnArgs& a, const int32_t* start, const int32_t* end, const uint32_t* hp, const int32_t* step,
+                   int layer) {
+  if (start == nullptr || end == nullptr || !a.causal || a.S != a.Skv) return false;
+  return (hp == nullptr && step == nullptr) || drop_ok(a, hp, step, layer);
+}
+
+PLX_API int plx_attn_doc_fwd(const AttnArgs* args, const int32_t* start, const int32_t* end, const uint32_t* hp,
+                             const int32_t* step, int layer, int D, hipStream_t stream) {
+  const AttnArgs& a = *args;
+  if (!args_ok(a, D) || !doc_ok(a, start, end, hp, step, layer)) return 1;
+  if (a.so.s % 4 || a.so.h % 4 || a.so.b % 4) return 1;
+  if (hp == nullptr) {
+    const AttnDocArgs ka{a, start, end};
+    return D == 128 ? launch_doc_fwd<128, false>(ka, stream) : launch_doc_fwd<64, false>(ka, stream);
+  }
+  const AttnDocDropArgs ka{{a, hp, step, (uint32_t)layer}, start, end};
+  return D == 128 ? launch_doc_fwd<128, true>(ka, stream) : launch_doc_fwd<64, true>(ka, stream);
+}
+
+PLX_API int plx_attn_doc_bwd(const AttnArgs* args, const int32_t* start, const int32_t* end, const uint32_t* hp,
+                             const int32_t* step, int layer, int D, float* ws, hipStream_t stream) {
+  const AttnArgs& a = *args;
+  if (const int rc = bwd_args_check(a, D, ws)) return rc;
+  if (!doc_ok(a, start, end, hp, step, layer)) return 1;
+  if (hp == nullptr) {
+    const AttnDocArgs ka{a, start, end};
+    return D == 128 ? launch_doc_bwd<128, false>(ka, ws, stream) : launch_doc_bwd<64, false>(ka, ws, stream);
+  }
+  const AttnDocDropArgs ka{{a, hp, step, (uint32_t)layer}, start, end};
+  return D == 128 ? launch_doc_bwd<128, true>(ka, ws, stream) : launch_doc_bwd<64, true>(ka, ws, stream);
+}
+
+PLX_API int plx_attn_doc_args_size() { return (int)sizeof(AttnArgs); }
+
+#elif !defined(PLX_ATTN_WIN)  // libplx_attn: the plain and the dropout entry points
 
 // forward waves per workgroup (A/B knob plx_attn_set_fwd_waves: 4 or 8)
 int g_fwd_waves = 8;

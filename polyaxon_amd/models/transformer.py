@@ -124,6 +124,7 @@ class Attention(nn.Module):
         self.proj = nn.Linear(cfg.n_heads * hd, cfg.d_model, bias=cfg.bias)
         self._drop = None  # (AttnDropoutState, layer index): Transformer.set_attn_dropout
         self._window = None  # AttnWindowState: Transformer.set_attn_window
+        self._doc = None  # AttnDocState: Transformer.set_attn_doc
         self._fp8 = False  # Transformer.set_fp8
         self._fp8_recipe = "tensor"
 
@@ -149,7 +150,10 @@ class Attention(nn.Module):
         # hand-written CDNA4 flash attention (ops/attention.py, csrc/attn_kernels.hip): GQA straight into the
         # kernel (no repeat_interleave of K/V), output written in [B, S, H, D] so the projection reads it as is
         drop = self._drop if self.training else None
-        if self._window is not None:
+        if self._doc is not None:
+            # document-masked attention over a packed row (ops/attn_doc.py): part of the model, like the window
+            y = flash_attention(q, k, v, causal=True, drop=drop, doc=self._doc)
+        elif self._window is not None:
             # sliding-window attention (ops/attn_window.py): part of the model, so train and eval alike
             y = flash_attention(q, k, v, causal=True, drop=drop, window=self._window)
         elif drop is not None:
@@ -258,6 +262,7 @@ class Transformer(nn.Module):
             self.logit_mask = None
         self._rope = None
         self._drop = None
+        self._doc = None
         self.reset_parameters()
 
     def set_dropout(self, state) -> None:
@@ -278,8 +283,21 @@ class Transformer(nn.Module):
     def set_attn_window(self, state) -> None:
         """Sliding-window attention with the window in device memory (ops/attn_window.py AttnWindowState): every
         block's attention sees the last W keys, in training and in ``eval()`` alike.  None: the plain attention call."""
+        if state is not None and self._doc is not None:
+            raise ValueError("sliding-window attention and document-masked attention do not combine")
         for blk in self.blocks:
             blk.attn._window = state
+
+    def set_attn_doc(self, state) -> None:
+        """Document-masked attention for packed sequences (ops/attn_doc.py AttnDocState): ``forward`` fills the
+        state's tables from its tokens once, and every block's attention stays inside the documents, in training, in
+        ``eval()`` and in checkpoint recomputation alike.  Positions are not reset per document.  None: the plain
+        attention call."""
+        if state is not None and any(blk.attn._window is not None for blk in self.blocks):
+            raise ValueError("sliding-window attention and document-masked attention do not combine")
+        self._doc = state
+        for blk in self.blocks:
+            blk.attn._doc = state
 
     def set_fp8(self, on: bool, recipe: str = "tensor") -> None:
         """The blocks' attention and MLP matrices on the FP8 GEMMs (ops/lm.py ``linear(fp8=True)``: E4M3 activations
@@ -319,6 +337,8 @@ class Transformer(nn.Module):
 
     def forward(self, tokens: torch.Tensor) -> torch.Tensor:
         B, S = tokens.shape
+        if self._doc is not None:  # the tables every block's attention reads, forward and backward
+            self._doc.update(tokens)
         x = self.embed(tokens)
         if self.head is None:  # tied head: its weight gradient may run on the side stream (lm_ops.linear side)
             x = lm_ops.join_before_backward(x)

@@ -46,6 +46,10 @@ LIBRARIES: Dict[str, dict] = {
     # windowed kernels must equal the plain ones bit for bit.  It costs nothing measurable (profiles/attn_window.md)
     "plx_attn_win": {"sources": ["attn_kernels.hip"], "kind": "hip", "link": [],
                      "flags": ["-DPLX_ATTN_WIN", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]},
+    # the document-mask instantiations of the same source (-DPLX_ATTN_DOC compiles those entry points and no others,
+    # ops/attn_doc.py): a library of its own with plx_attn_win's flags, loaded only when a document state is used
+    "plx_attn_doc": {"sources": ["attn_kernels.hip"], "kind": "hip", "link": [],
+                     "flags": ["-DPLX_ATTN_DOC", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]},
     # Muon's batched Newton-Schulz GEMMs and passes: a library of its own (no other binary changes), built without
     # packed fp32 arithmetic like the other new libraries
     "plx_muon": {"sources": ["muon_kernels.hip"], "kind": "hip", "link": [],
@@ -430,6 +434,11 @@ SIGNATURES: Dict[str, Dict[str, list]] = {
         "plx_attn_win_fwd": [_P, _P, _P, _P, _I, _I, _P],  # (AttnArgs*, win, hp, step, layer, D, stream)
         "plx_attn_win_bwd": [_P, _P, _P, _P, _I, _I, _P, _P],  # (AttnArgs*, win, hp, step, layer, D, ws, stream)
         "plx_attn_win_args_size": [],
+    },
+    "plx_attn_doc": {  # hp / step: both null (no dropout) or both set
+        "plx_attn_doc_fwd": [_P, _P, _P, _P, _P, _I, _I, _P],  # (AttnArgs*, start, end, hp, step, layer, D, stream)
+        "plx_attn_doc_bwd": [_P, _P, _P, _P, _P, _I, _I, _P, _P],  # (.., layer, D, ws, stream)
+        "plx_attn_doc_args_size": [],
     },
     "plx_pool": {
         "plx_maxpool3s2_forward": [_P, _P, _P, _I, _I, _I, _I, _P],

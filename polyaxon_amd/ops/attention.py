@@ -19,6 +19,11 @@ the forward and in both backward kernels; nothing is stored.  ``drop=None`` is e
 int32 of device memory that the ``plx_attn_win_*`` entry points (the 8-wave kernels' band variants, a library of
 their own) read at run time; it composes with ``drop``.  Causal self-attention only.  ``window=None`` is exactly
 the calls above.
+
+``doc=AttnDocState`` is document-masked attention for packed sequences (ops/attn_doc.py): query i of row b sees keys
+``start[b][i] <= j <= i``, the two int32 ``[B, S]`` tables device data that the ``plx_attn_doc_*`` entry points (the
+8-wave kernels' document variants, a library of their own) read at run time; it composes with ``drop``, not with
+``window``.  Causal self-attention only.  ``doc=None`` is exactly the calls above.
 """
 from __future__ import annotations
 
@@ -92,11 +97,12 @@ def _reference_mask(drop, B, H, S, Skv, device):
     return torch.from_numpy(m.reshape(B, H, S, Skv)).to(device=device, dtype=torch.float32) * state.c
 
 
-def _reference(q, k, v, causal, scale, drop=None, window=None):
+def _reference(q, k, v, causal, scale, drop=None, window=None, doc=None):
     """Plain fp32 math (matmul + softmax): the CPU path and the path for shapes / dtypes the HIP kernel does not
     take (fp32 reference models, head_dim other than 64 / 128).  No SDPA, so no library attention kernel.  ``drop``:
     the softmax is multiplied by the twin's scaled mask (ops/attn_dropout.py).  ``window``: the band of the state's
-    host value (ops/attn_window.py) joins the causal mask."""
+    host value (ops/attn_window.py) joins the causal mask.  ``doc``: so does key j < start[b][i] of the state's table
+    (ops/attn_doc.py)."""
     rep = q.shape[1] // k.shape[1]
     kk = k.repeat_interleave(rep, 1) if rep > 1 else k
     vv = v.repeat_interleave(rep, 1) if rep > 1 else v
@@ -106,6 +112,8 @@ def _reference(q, k, v, causal, scale, drop=None, window=None):
         hidden = torch.ones(S, Sk, dtype=torch.bool, device=q.device).triu(1)
         if window is not None and window.W > 0:  # key j <= i - W lies before the window of query i
             hidden |= torch.ones(S, Sk, dtype=torch.bool, device=q.device).tril(-window.W)
+        if doc is not None:  # [B, 1, S, Sk]: key j lies before the document of query i
+            hidden = hidden | (torch.arange(Sk, device=q.device)[None, None, None, :] < doc.start[:, None, :, None])
         s = s.masked_fill(hidden, float("-inf"))
     p = s.softmax(-1)
     if drop is not None:
@@ -141,8 +149,21 @@ def _win_lib():
     return lib
 
 
+_DOC_CHECKED = False
+
+
+def _doc_lib():
+    """The document-mask library (the same source and argument block as :func:`_lib`'s, built on its own)."""
+    global _DOC_CHECKED
+    lib = _native.lib("plx_attn_doc")
+    if not _DOC_CHECKED:
+        _check(lib.plx_attn_doc_args_size())
+        _DOC_CHECKED = True
+    return lib
+
+
 def _drop_ptrs(drop):
-    """(hp, step, layer) of the windowed entry points: null pointers without dropout"""
+    """(hp, step, layer) of the windowed and the document entry points: null pointers without dropout"""
     if drop is None:
         return None, None, 0
     state, layer = drop
@@ -151,7 +172,7 @@ def _drop_ptrs(drop):
 
 class _FlashAttention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, causal: bool, scale: float, drop=None, window=None):
+    def forward(ctx, q, k, v, causal: bool, scale: float, drop=None, window=None, doc=None):
         lib = _lib()
         q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
         B, H, S, D = q.shape
@@ -160,7 +181,11 @@ class _FlashAttention(torch.autograd.Function):
         a = _args(q, k, v, causal, scale)
         a.out, a.so, a.lse2 = out.data_ptr(), _bhs(out, "bshd"), lse2.data_ptr()
         stream = torch.cuda.current_stream(q.device).cuda_stream
-        if window is not None:
+        if doc is not None:
+            rc = _doc_lib().plx_attn_doc_fwd(ctypes.byref(a), doc.start.data_ptr(), doc.end.data_ptr(),
+                                             *_drop_ptrs(drop), D, stream)
+            _native.check(rc, "plx_attn_doc_fwd")
+        elif window is not None:
             rc = _win_lib().plx_attn_win_fwd(ctypes.byref(a), window.win.data_ptr(), *_drop_ptrs(drop), D, stream)
             _native.check(rc, "plx_attn_win_fwd")
         elif drop is None:
@@ -171,7 +196,7 @@ class _FlashAttention(torch.autograd.Function):
                                        stream)
             _native.check(rc, "plx_attn_drop_fwd")
         ctx.save_for_backward(q, k, v, out, lse2)
-        ctx.causal, ctx.scale, ctx.drop, ctx.window = causal, scale, drop, window
+        ctx.causal, ctx.scale, ctx.drop, ctx.window, ctx.doc = causal, scale, drop, window, doc
         return out
 
     @staticmethod
@@ -193,7 +218,11 @@ class _FlashAttention(torch.autograd.Function):
         ws = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=q.device) if nbytes else None
         wsp = ws.data_ptr() if ws is not None else None
         stream = torch.cuda.current_stream(q.device).cuda_stream
-        if ctx.window is not None:  # the word the forward read: nothing may set the window in between
+        if ctx.doc is not None:  # the tables the forward read: nothing may update them in between
+            rc = _doc_lib().plx_attn_doc_bwd(ctypes.byref(a), ctx.doc.start.data_ptr(), ctx.doc.end.data_ptr(),
+                                             *_drop_ptrs(ctx.drop), D, wsp, stream)
+            _native.check(rc, "plx_attn_doc_bwd")
+        elif ctx.window is not None:  # the word the forward read: nothing may set the window in between
             rc = _win_lib().plx_attn_win_bwd(ctypes.byref(a), ctx.window.win.data_ptr(), *_drop_ptrs(ctx.drop), D, wsp,
                                              stream)
             _native.check(rc, "plx_attn_win_bwd")
@@ -204,23 +233,31 @@ class _FlashAttention(torch.autograd.Function):
             rc = lib.plx_attn_drop_bwd(ctypes.byref(a), state.hp.data_ptr(), state.step_counter.data_ptr(), layer, D,
                                        wsp, stream)
             _native.check(rc, "plx_attn_drop_bwd")
-        return dq, dk, dv, None, None, None, None
+        return dq, dk, dv, None, None, None, None, None
 
 
 def flash_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal: bool = True,
-                    scale: Optional[float] = None, drop=None, window=None) -> torch.Tensor:
+                    scale: Optional[float] = None, drop=None, window=None, doc=None) -> torch.Tensor:
     """softmax(q k^T * scale [+ causal mask]) v with GQA (H % Hkv == 0).  q: [B,H,S,D], k/v: [B,Hkv,Skv,D].
     Returns [B, S, H, D].  ``drop=(AttnDropoutState, layer)``: dropout on the probabilities; ``window=AttnWindowState``:
-    each query sees its last W keys, causal self-attention only (module docstring)."""
+    each query sees its last W keys, causal self-attention only; ``doc=AttnDocState``: each query sees the keys of
+    its own document in a packed row, causal self-attention only, no window (module docstring)."""
     if q.dim() != 4 or k.dim() != 4 or v.shape != k.shape or q.shape[-1] != k.shape[-1]:
         raise ValueError("expected q [B,H,S,D] and k/v [B,Hkv,Skv,D]")
     if q.shape[1] % k.shape[1]:
         raise ValueError("query heads must be a multiple of key/value heads")
     if window is not None and (not causal or q.shape[2] != k.shape[2]):
         raise ValueError("window= is causal self-attention only: causal=True and S == Skv")
+    if doc is not None:
+        if not causal or q.shape[2] != k.shape[2] or window is not None:
+            raise ValueError("doc= is causal self-attention only, without a window: causal=True, S == Skv, window=None")
+        if tuple(doc.start.shape) != (q.shape[0], q.shape[2]):
+            raise ValueError(f"doc= tables are {tuple(doc.start.shape)}, q is [B, S] = {(q.shape[0], q.shape[2])}")
     scale = 1.0 / math.sqrt(q.shape[-1]) if scale is None else float(scale)
     if not q.is_cuda or q.dtype != torch.bfloat16 or q.shape[-1] not in (64, 128):
-        return _reference(q, k, v, causal, scale, drop, window)
+        return _reference(q, k, v, causal, scale, drop, window, doc)
+    if doc is not None:
+        return _FlashAttention.apply(q, k, v, causal, scale, drop, None, doc)
     if window is not None:
         return _FlashAttention.apply(q, k, v, causal, scale, drop, window)
     if drop is None:

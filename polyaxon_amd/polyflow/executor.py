@@ -54,7 +54,8 @@ class ResidentTrialExecutor:
                  lp_dtype: Optional[torch.dtype] = None, clip_grad: bool = False, lr_schedule=False,
                  loss_hparams: bool = False, dropout: bool = False, dropout_seed: int = 0,
                  attn_dropout: bool = False, layerwise: bool = False, attn_window: bool = False,
-                 muon=None, fp8: bool = False, fp8_recipe: str = "tensor", aux_loss: Optional[Callable] = None):
+                 muon=None, fp8: bool = False, fp8_recipe: str = "tensor", aux_loss: Optional[Callable] = None,
+                 attn_doc: Optional[int] = None):
         """``lp_dtype`` (the language models, GPU): the model computes from bf16 weights with bf16 gradients and the
         optimizer keeps the fp32 master (ops/flat.py lp mode); every re-init / restore refreshes the bf16 copy.
         ``clip_grad``: global-norm gradient clipping (ops/optim.py) with ``max_grad_norm`` as one more device
@@ -93,7 +94,13 @@ class ResidentTrialExecutor:
         ``fp8_recipe``: ``"tensor"`` (that) or ``"mx"`` (one E8M0 scale per 32 values, csrc/gemm_mxfp8.hip); anything
         but the default needs ``fp8=True``.
         ``aux_loss``: called with no argument after the forward; the scalar it returns (a mixture-of-experts model's
-        weighted load-balance term) is added to the loss the step trains on, not to the one the metric ring records."""
+        weighted load-balance term) is added to the loss the step trains on, not to the one the metric ring records.
+        ``attn_doc`` (an EOS token id): document-masked attention for packed sequences (ops/attn_doc.py): the model's
+        ``set_attn_doc`` gets a state built at this executor's batch and sequence, its forward refills the tables from
+        every batch inside the step, and its attention runs the document flash-attention kernels.  Part of the
+        program, not a per-trial value; not together with ``attn_window``."""
+        if attn_doc is not None and attn_window:
+            raise ValueError("attn_doc and attn_window cannot be combined: the document kernels have no window")
         self.aux_loss = aux_loss
         self.device = torch.device(device)
         self.is_cuda = self.device.type == "cuda"
@@ -187,6 +194,14 @@ class ResidentTrialExecutor:
             self.x, self.y = self.data.x, self.data.y
         else:
             self.x, self.y = batch[0].to(self.device), batch[1].to(self.device)
+        self.attn_doc = None
+        if attn_doc is not None:
+            if not hasattr(model, "set_attn_doc"):
+                raise ValueError(f"attn_doc needs a model with set_attn_doc(); {type(model).__name__} has no attention")
+            from polyaxon_amd.ops.attn_doc import AttnDocState
+
+            self.attn_doc = AttnDocState(self.device, self.x.shape[0], self.x.shape[1], attn_doc)
+            model.set_attn_doc(self.attn_doc)
         self.amp_dtype = amp_dtype if self.is_cuda else None
         self.ring_size = ring_size
         self.ring = torch.zeros(ring_size, dtype=torch.float32, device=self.device)

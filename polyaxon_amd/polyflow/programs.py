@@ -45,6 +45,12 @@ the windowed flash-attention kernels) with the window ``attn_window`` -- keys pe
 per-trial hyper-parameter, 0 (no window) until a trial sets it.  It composes with ``attn_dropout`` and ``dropout``.
 The other programs reject it.
 
+``gpt2`` and ``gpt2_tiny`` also take ``params: {attn_doc_eos: <token id>}``: document-masked attention for packed
+sequences (ops/attn_doc.py, the document flash-attention kernels): a document ends with that token, and every query
+sees the keys of its own document only.  The tables are rebuilt from each batch inside the step.  It is part of the
+program, not a per-trial value, composes with ``attn_dropout`` and ``dropout`` and is refused together with
+``attn_window``.  The other programs reject it.
+
 ``gpt2`` and ``gpt2_tiny`` also take ``params: {muon: true}``: Muon on the blocks' attention and MLP weight matrices
 (ops/optim.py, csrc/muon_kernels.hip; the embeddings and everything 1-D stay on AdamW) with ``muon_lr`` and
 ``muon_momentum`` as per-trial hyper-parameters, 0.02 and 0.95 until a trial sets them.  Not together with
@@ -191,6 +197,18 @@ def _attn_window(params: Dict[str, Any]) -> bool:
     return bool(params.get("attn_window", False))
 
 
+def _attn_doc(params: Dict[str, Any]) -> Optional[int]:
+    """The EOS token id of ``attn_doc_eos``, or None without it; refused beside ``attn_window``."""
+    if params.get("attn_doc_eos") is None:
+        return None
+    from polyaxon_amd.ops import attn_doc
+
+    eos = attn_doc.validate(params["attn_doc_eos"])
+    if _attn_window(params):
+        raise ValueError("`attn_doc_eos` and `attn_window` cannot be combined: the document kernels have no window")
+    return eos
+
+
 def _fp8(params: Dict[str, Any]) -> bool:
     from polyaxon_amd.ops import fp8
 
@@ -237,6 +255,8 @@ def _no_dropout(name: str, params: Dict[str, Any]) -> None:
         raise ValueError(f"program {name} has no attention: `attn_dropout` is a param of gpt2 / gpt2_tiny only")
     if _attn_window(params):
         raise ValueError(f"program {name} has no attention: `attn_window` is a param of gpt2 / gpt2_tiny only")
+    if params.get("attn_doc_eos") is not None:
+        raise ValueError(f"program {name} has no attention: `attn_doc_eos` is a param of gpt2 / gpt2_tiny only")
     if _muon(params):
         raise ValueError(f"program {name} has no transformer blocks: `muon` is a param of gpt2 / gpt2_tiny only")
 
@@ -374,6 +394,7 @@ def _gpt2(params: Dict[str, Any], device, tiny: bool) -> TrialProgram:
     from polyaxon_amd.polyflow.executor import ResidentTrialExecutor
 
     dev = torch.device(device)
+    doc_eos = _attn_doc(params)
     experts, top_k, aux_coef = _moe(params)
     moe = {"n_experts": experts, "moe_top_k": top_k} if experts else {}
     if tiny:
@@ -409,7 +430,8 @@ def _gpt2(params: Dict[str, Any], device, tiny: bool) -> TrialProgram:
                                muon=muon_parameter_names(model) if _muon(params) else None,
                                fp8=_fp8(params), fp8_recipe=_fp8_recipe(params),
                                # trains on NLL + c * balance term; the metric ring keeps the plain NLL
-                               aux_loss=(lambda: aux_coef * model.moe_aux()) if experts else None)
+                               aux_loss=(lambda: aux_coef * model.moe_aux()) if experts else None,
+                               attn_doc=doc_eos)
     prog = _with_layerwise(_with_attn_dropout(_with_dropout(_with_loss_hp(_with_schedule(_with_clip(TrialProgram(
         ex, unit_steps=int(params.get("unit_steps", 4 if tiny else 10)),
         window=int(params.get("window", 4)),
@@ -426,6 +448,8 @@ def _gpt2(params: Dict[str, Any], device, tiny: bool) -> TrialProgram:
         prog.info["fp8"] = True
         if _fp8_recipe(params) != "tensor":
             prog.info["fp8_recipe"] = _fp8_recipe(params)
+    if doc_eos is not None:
+        prog.info["attn_doc_eos"] = doc_eos
     if experts:
         prog.info["moe"] = {"experts": experts, "top_k": top_k, "aux_coef": aux_coef}
     return _with_muon(_with_attn_window(prog, _attn_window(params)), _muon(params))

@@ -259,6 +259,10 @@ def train_lm(argv=None) -> float:
                     help="sliding-window attention: every query sees its last N keys (ops/attn_window.py: device data "
                          "of the windowed flash-attention kernels, training and evaluation alike); 0: no state, the "
                          "plain kernels")
+    ap.add_argument("--attn-doc-eos", "--attn_doc_eos", dest="attn_doc_eos", type=int, default=None, metavar="ID",
+                    help="document-masked attention for packed sequences: token ID ends a document and every query "
+                         "sees the keys of its own document only (ops/attn_doc.py: device tables of the document "
+                         "flash-attention kernels, rebuilt from every batch); not with --attn-window")
     ap.add_argument("--fp8", action="store_true",
                     help="the blocks' attention and MLP linears on the FP8 GEMMs (ops/fp8.py, csrc/gemm_fp8.hip: E4M3 "
                          "activations and weights, E5M2 output gradients, per-tensor device scales); off: the bf16 "
@@ -375,6 +379,12 @@ def train_lm(argv=None) -> float:
         from polyaxon_amd.ops.attn_window import AttnWindowState
 
         model.set_attn_window(AttnWindowState(dev, args.attn_window))
+    if args.attn_doc_eos is not None:  # device tables of the document attention kernels; unset: not built at all
+        if args.attn_window != 0:
+            raise SystemExit("--attn-doc-eos and --attn-window cannot be combined")
+        from polyaxon_amd.ops.attn_doc import AttnDocState
+
+        model.set_attn_doc(AttnDocState(dev, args.bs, seq, args.attn_doc_eos))
     if args.fp8_recipe is not None and not args.fp8:
         raise SystemExit("--fp8-recipe needs --fp8")
     if args.fp8:
