@@ -654,12 +654,19 @@ __global__ __launch_bounds__(64) void lr_schedule_kernel(const float* __restrict
 }  // namespace
 
 // The optimizer launches, shared by the plain entry points (state == nullptr: the kernels without clipping) and the
-// *_clip ones.
+// *_clip ones.  Each refuses (returns 1, launches nothing) a negative n and what its kernel would dereference: a null
+// hyper-parameter vector or step counter -- read by every lane, whatever n -- and a null buffer with n > 0.
 namespace {
+
+template <typename... Ptr>
+bool any_null(Ptr... ptr) {
+  return ((ptr == nullptr) || ...);
+}
 
 int launch_sgd_flat(float* p, float* g, float* m, int64_t n, int64_t n_decay, const float* hp, const int* first_step,
                     const float* state, hipStream_t stream) {
   if ((n & 3) || (n_decay & 3)) return 1;  // caller pads flat buffers to a multiple of 4 floats
+  if (n < 0 || hp == nullptr || (n > 0 && any_null(p, g, m))) return 1;  // first_step may be null: never a first step
   const int64_t nv = n >> 2;
   if (state != nullptr)
     hipLaunchKernelGGL((sgd_flat_kernel<true, const float*>), dim3(grid_for(nv)), dim3(kBlock), 0, stream, (float4*)p, (float4*)g,
@@ -673,6 +680,7 @@ int launch_sgd_flat(float* p, float* g, float* m, int64_t n, int64_t n_decay, co
 int launch_adamw_flat(float* p, float* g, float* m, float* v, int64_t n, int64_t n_decay, const float* hp,
                       const int* step, const float* state, hipStream_t stream) {
   if ((n & 3) || (n_decay & 3)) return 1;
+  if (n < 0 || any_null(hp, step) || (n > 0 && any_null(p, g, m, v))) return 1;
   const int64_t nv = n >> 2;
   const dim3 grid(grid_for(nv, g_adamw_grid_cap));
   if (state != nullptr)
@@ -687,6 +695,7 @@ int launch_adamw_flat(float* p, float* g, float* m, float* v, int64_t n, int64_t
 int launch_adamw_mixed(float* p, void* g, float* m, float* v, void* plp, int64_t n, int decay_on, const float* hp,
                        const int* step, const float* state, hipStream_t stream) {
   if (n & 3) return 1;
+  if (n < 0 || any_null(hp, step) || (n > 0 && any_null(p, g, m, v, plp))) return 1;
   const bool aligned = ((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)plp) % 16 == 0;
   if (g_adamw_wide && (n & 7) == 0 && aligned) {
     const int64_t n8 = n >> 3;
@@ -783,7 +792,7 @@ PLX_API int plx_adamw_mixed_clip(float* p, void* g, float* m, float* v, void* pl
 }
 
 PLX_API int plx_cast_lp(const float* p, void* plp, int64_t n, hipStream_t stream) {
-  if (n & 3) return 1;
+  if ((n & 3) || n < 0 || (n > 0 && (p == nullptr || plp == nullptr))) return 1;
   hipLaunchKernelGGL(cast_lp_kernel, dim3(grid_for(n >> 2)), dim3(kBlock), 0, stream, (const float4*)p,
                      (u16x4*)plp, n >> 2);
   return (int)hipGetLastError();
